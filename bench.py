@@ -10,18 +10,28 @@ Run: python bench.py --gpus N --steps K --warmup W.  N > 1 runs one rank per GPU
 torch.distributed.run as launched by the driver, or -- started plainly -- bench.py itself starts
 torch.distributed.run with N ranks as a child process before touching the GPU.  A WORLD_SIZE from a
 launcher that disagrees with --gpus is an error.
-A plain N = 1 run (no --workload) is a suite: the EDSR_Lx4 headline (C2) plus one sub-record per
-other BASELINE config in the same HR-pixels/s unit (rcan = C3, swinir = C4, rrdb = C5), each
-measured in its own child process by `bench.py --workload X` (run_suite; the parent never touches
-the GPU).  `--workload X` measures one workload in this process; `--lr-px 256` is the SURVEY §8
-secondary sweep (LR 256 -> HR 1024).
-Prints ONE JSON line on rank 0 with the roofline of the dominant kernel (HIP events on an
-untimed warm-up step; bound chosen from its arithmetic intensity against the 312 FLOP/B
-ridge), the CPU baseline (oracle restatement of the same workload's train step on the host
-cores, bounded sample, rank 0 at N=1) and the parity of the benchmarked net against the CPU
-oracle on one LR tile (fp32 max-abs, bf16 PSNR; rank 0 at N=1, outside the timed region).
+A plain run does only what the headline figure needs: it builds the model, warms up (at least the
+3 steps a HIP-graph capture takes), times the K steps, writes `--dump-outputs DIR` if asked and
+prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step,
+config; roofline / cpu_baseline / parity null).  `--workload X` picks another BASELINE workload
+than the EDSR headline; `--lr-px 256` is the SURVEY §8 secondary sweep (LR 256 -> HR 1024).
+`--dump-outputs DIR` writes what the last timed step left its caller as DIR/<name>.npy (float32):
+`output` (the SR batch), `loss` (l_pix), and `params`, `params_ema`, `grads` (the flat parameter,
+EMA and gradient buffers); an array above its element budget is a fixed, seeded sample of its
+flattened elements (_sample), at most 64 MB in all.  Inputs and initial weights are seeded, so two
+builds run with the same arguments can be compared array for array.
+`--full` adds everything else.  At N = 1 without --workload it is a suite: the EDSR_Lx4 headline
+(C2) plus one sub-record per other BASELINE config in the same HR-pixels/s unit (rcan = C3,
+swinir = C4, rrdb = C5), each measured in its own child process by `bench.py --full --workload X`
+(run_suite; the parent never touches the GPU).  Each `--full` line carries the roofline of the
+dominant kernel (HIP events on an untimed warm-up step; bound chosen from its arithmetic intensity
+against the 312 FLOP/B ridge), the CPU baseline (oracle restatement of the same workload's train
+step on the host cores, bounded sample, rank 0 at N=1) and the parity of the benchmarked net
+against the CPU oracle on one LR tile (fp32 max-abs, bf16 PSNR; rank 0 at N=1, outside the timed
+region); --no-trace / --no-cpu-baseline / --no-parity drop one of them again.
 """
 import argparse
+import contextlib
 import json
 import math
 import os
@@ -65,7 +75,7 @@ WORKLOADS = {
 }
 # BASELINE.json config each workload line is quoted on
 BASELINE_CONFIG = {'edsr': 'configs[1]', 'rcan': 'configs[2]', 'swinir': 'configs[3]', 'rrdb': 'configs[4]'}
-# the workloads a plain `python bench.py` (N = 1) reports beside the EDSR headline, one child process each
+# the workloads `python bench.py --full` (N = 1) reports beside the EDSR headline, one child process each
 SUB_WORKLOADS = ('rcan', 'swinir', 'rrdb')
 
 
@@ -379,6 +389,41 @@ def roofline(workload, kstats, traced_steps, step_s, use_graph):
     return roof
 
 
+# --dump-outputs element budgets (float32: 4 bytes each, 56 MB + the loss in all, under the 64 MB cap)
+DUMP_BUDGET = {'output': 8 << 20, 'params': 2 << 20, 'params_ema': 2 << 20, 'grads': 2 << 20}
+
+
+def _sample(t, budget):
+    """``t`` flattened, as float32 on the host; above ``budget`` elements the ones at ``budget`` sorted
+    indices drawn once from a CPU generator seeded with the element count (so two builds sample the
+    same elements of the same-sized array)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > budget:
+        g = torch.Generator().manual_seed(flat.numel())
+        idx = torch.randint(0, flat.numel(), (budget,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(model, loss, out_dir):
+    """What the last timed step left its caller (--dump-outputs): the SR batch ``model.output``, the
+    logged loss, and the flat parameter / EMA / gradient buffers the step updated, each as
+    ``out_dir/<name>.npy`` (float32; _sample above DUMP_BUDGET)."""
+    import numpy as np
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'output': model.output, 'loss': torch.tensor([loss], dtype=torch.float32)}
+    if model.flat_g is not None:
+        arrays['params'], arrays['grads'] = model.flat_g.flat, model.flat_g.grad
+    if model.flat_ema is not None:
+        arrays['params_ema'] = model.flat_ema.flat
+    for name, t in arrays.items():
+        a = _sample(t, DUMP_BUDGET.get(name, 1 << 20))
+        if name == 'output' and a.size == t.numel():
+            a = a.reshape(tuple(t.shape))
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -463,9 +508,10 @@ def _compact(line):
 
 
 def run_suite(args):
-    """A plain ``python bench.py`` at N = 1: the EDSR headline and one sub-record per other BASELINE
-    workload (SUB_WORKLOADS), each measured by ``bench.py --workload X`` in a CHILD process with the
-    same --steps / --warmup.  This process never touches the GPU (it only starts the children, one
+    """``python bench.py --full`` at N = 1: the EDSR headline and one sub-record per other BASELINE
+    workload (SUB_WORKLOADS), each measured by ``bench.py --full --workload X`` in a CHILD process with
+    the same --steps / --warmup (--dump-outputs goes to the headline child alone).
+    This process never touches the GPU (it only starts the children, one
     after another, and merges their JSON lines), so every child starts on an idle, freshly
     initialised device.  The printed line is the headline child's line unchanged (value, timing,
     roofline, cpu_baseline of EDSR_Lx4 B 32), plus ``workloads``: a compact summary of all four
@@ -473,7 +519,7 @@ def run_suite(args):
     MFMA fractions) and ``sub_records``: each child's full line.  Exit status: the headline child's;
     a failed sub-workload is recorded in its entry (``rc``) and on stderr."""
     import subprocess
-    base = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', str(args.steps),
+    base = [sys.executable, os.path.abspath(__file__), '--full', '--gpus', '1', '--steps', str(args.steps),
             '--warmup', str(args.warmup), '--graph', str(args.graph)]
     for flag in ('no_cpu_baseline', 'no_trace', 'no_parity', 'ddp', 'dry_run'):
         if getattr(args, flag):
@@ -487,6 +533,8 @@ def run_suite(args):
     lines, rcs, walls = {}, {}, {}
     for wl in ('edsr',) + tuple(w for w in args.sub_workloads.split(',') if w):
         cmd = base + ['--workload', wl, '--cpu-seconds', str(args.cpu_seconds if wl == 'edsr' else args.sub_cpu_seconds)]
+        if wl == 'edsr' and args.dump_outputs:
+            cmd += ['--dump-outputs', args.dump_outputs]
         t0 = time.time()
         try:
             p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True, timeout=args.child_timeout)
@@ -507,7 +555,7 @@ def run_suite(args):
             return rc or 1
     line = dict(lines['edsr'])
     line['suite'] = {'parent_touches_gpu': False, 'child_wall_s': walls,
-                     'note': 'each workload measured by `bench.py --workload X` in its own child process'}
+                     'note': 'each workload measured by `bench.py --full --workload X` in its own child process'}
     line['sub_records'] = {wl: lines[wl] for wl in lines if wl != 'edsr'}
     line['workloads'] = {}
     for wl in lines:
@@ -524,11 +572,19 @@ def main():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=0, help='per-GPU batch (0: the workload default)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: per-kernel trace and roofline, CPU '
+                         'baseline, parity against the CPU oracle, and (N = 1, no --workload) the other workloads '
+                         'as sub-records')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps write what the last step computed (output, loss, parameter / EMA / '
+                         'gradient samples) as DIR/<name>.npy, float32, at most 64 MB in all')
     ap.add_argument('--workload', default=None, choices=sorted(WORKLOADS),
-                    help='measure one workload in this process (default: the EDSR headline, plus the '
-                         '--sub-workloads as sub-records at N = 1, each in a child process)')
+                    help='measure one workload in this process (default: the EDSR headline; with --full at N = 1 '
+                         'plus the --sub-workloads as sub-records, each in a child process)')
     ap.add_argument('--sub-workloads', default=','.join(SUB_WORKLOADS),
-                    help='comma list reported beside the headline when --workload is not given at N = 1 ("" none)')
+                    help='comma list reported beside the headline by --full when --workload is not given at N = 1 '
+                         '("" none)')
     ap.add_argument('--lr-px', type=int, default=0,
                     help='LR tile side (0: the workload default, 64; RRDB 128); HR = 4x (SURVEY §8 sweep: 256)')
     ap.add_argument('--cpu-seconds', type=float, default=20.0, help='CPU-baseline sample budget (s)')
@@ -547,6 +603,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error('--gpus must be >= 1')
+    if args.steps < 1:
+        ap.error('--steps must be >= 1')
+    if not args.full:  # a plain run: the timed steps and nothing beside them
+        args.no_trace = args.no_parity = args.no_cpu_baseline = True
 
     env_world = os.environ.get('WORLD_SIZE')
     if env_world is None and args.gpus > 1:
@@ -559,8 +619,8 @@ def main():
     rank = int(os.environ.get('RANK', '0'))
     local = int(os.environ.get('LOCAL_RANK', '0'))
     if args.workload is None:
-        if env_world is None and args.sub_workloads:
-            sys.exit(run_suite(args))  # N = 1, plain start: headline + sub-records in child processes
+        if args.full and env_world is None and args.sub_workloads:
+            sys.exit(run_suite(args))  # N = 1, --full, no launcher: headline + sub-records in child processes
         args.workload = 'edsr'
     if args.dry_run:
         return dry_run(args, world, rank)
@@ -594,8 +654,9 @@ def main():
     use_graph = (GRAPH_DEFAULT.get(args.workload, True) or ddp) if args.graph < 0 else bool(args.graph)
     opt = make_opt(world, B, args.workload, use_graph, ddp=ddp, shared_gpu=shared_gpu)
     opt['rank'] = rank
-    model = build_model(opt)
-    g0 = torch.Generator(device=dev).manual_seed(0 + rank)
+    with contextlib.redirect_stdout(sys.stderr):  # the model prints its size: stdout carries the JSON line alone
+        model = build_model(opt)
+    g0 =torch.Generator(device=dev).manual_seed(0 + rank)
     g1 = torch.Generator(device=dev).manual_seed(1 + rank)
     lq = torch.rand(B, 3, lr_px, lr_px, generator=g0, device=dev)
     gt = torch.rand(B, 3, 4 * lr_px, 4 * lr_px, generator=g1, device=dev)
@@ -652,13 +713,16 @@ def main():
             print(json.dumps({'rank': rank, 'step_trace': os.environ['SR_STEP_TRACE'], 'phases_ms': ph,
                               'total_ms': round((tr[-1][1] - tr[0][1]) * 1e3, 3)}), file=sys.stderr)
 
+    if rank == 0 and args.dump_outputs:  # before the roofline re-launches touch any of the step's buffers
+        dump_outputs(model, loss, args.dump_outputs)
+
     hr_px = world * B * hr_px_tile * args.steps
     value = hr_px / dt
     roof = None
     if kstats:
         roof = roofline(args.workload, kstats, traced_steps, dt / args.steps, use_graph)
     cpu = parity = swin_att = None
-    if rank == 0 and args.workload == 'swinir':
+    if rank == 0 and args.full and args.workload == 'swinir':
         swin_att = swin_fused_roofline(model, B, lr_px, dev)
     if rank == 0 and world == 1 and not args.no_parity:
         parity = parity_check(args.workload, dev)

@@ -63,11 +63,11 @@ def test_pmc_traffic_record_per_dominant_kernel():
 
 
 def test_bench_suite_sub_records_per_workload():
-    """A plain N = 1 run measures the EDSR headline and RCAN / SwinIR / RRDB each in a child
+    """A ``--full`` N = 1 run measures the EDSR headline and RCAN / SwinIR / RRDB each in a child
     process (the parent never touches the GPU) and prints ONE line: the headline's fields, then
     ``workloads`` as the last key (the driver keeps the tail of stdout) with one compact record per
     BASELINE config."""
-    p = _run(['--dry-run', '--steps', '2'])
+    p = _run(['--full', '--dry-run', '--steps', '2'])
     assert p.returncode == 0, p.stderr[-3000:]
     d = _line(p)
     assert d['config']['model'] == 'EDSR' and d['config']['baseline_config'] == 'configs[1]'
@@ -89,3 +89,36 @@ def test_bench_lr_px_sweep_label():
     d = _line(p)
     assert d['config']['lr_tile'] == 256 and 'LR 256x256 -> HR 1024x1024' in d['config']['workload']
     assert d['config']['per_gpu_batch'] == 2
+
+
+def test_bench_plain_run_is_headline_only():
+    """Without ``--full`` an N = 1 run is the EDSR headline alone, in this process: no suite, no
+    sub-records, and the steps / warm-up it was asked for."""
+    p = _run(['--gpus', '1', '--dry-run', '--steps', '4', '--warmup', '5'])
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = _line(p)
+    assert d['config']['model'] == 'EDSR' and d['config']['baseline_config'] == 'configs[1]'
+    assert d['steps'] == 4 and d['warmup'] == 5
+    assert 'suite' not in d and 'workloads' not in d and 'sub_records' not in d
+    assert 'done in' not in p.stderr  # run_suite's per-child progress lines
+
+
+def test_bench_rejects_zero_steps():
+    p = _run(['--dry-run', '--steps', '0'])
+    assert p.returncode != 0 and '--steps must be >= 1' in p.stderr
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs: an array within its budget is written whole, a larger one as the same
+    ``budget`` elements on every call (indices seeded by the element count, ascending)."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    t = torch.arange(1000, dtype=torch.float64).reshape(10, 100)
+    whole = bench._sample(t, 1000)
+    assert whole.dtype == np.float32 and np.array_equal(whole, np.arange(1000, dtype=np.float32))
+    a, b = bench._sample(t, 64), bench._sample(t.clone(), 64)
+    assert a.dtype == np.float32 and a.shape == (64,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) >= 0) and a.min() >= 0 and a.max() <= 999 and len(np.unique(a)) > 32
+    assert 4 * (sum(bench.DUMP_BUDGET.values()) + (1 << 20)) <= 64 << 20

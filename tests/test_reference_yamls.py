@@ -1,11 +1,12 @@
 """The reference's own hot-path option files (north_star: "options/train YAMLs ... still work"):
-every EDSR / RCAN / SwinIR / RRDBNet-PSNR / MSRResNet train and test YAML of /root/reference is
+every EDSR / RCAN / SwinIR / RRDBNet-PSNR / MSRResNet train and test YAML of the reference (stored
+unchanged under tests/golden/reference_options/, same relative paths as its options/ folder) is
 read by this package's ``parse_options`` (basicsr/utils/options.py:99-201 contract) and its
 ``network_g`` built by ``build_network`` (basicsr/archs/__init__.py:18-24) with the reference's
 kwargs; ``model_type``, the pixel loss, the scheduler and the optimizer must resolve to what this
 package implements, and the datasets to registered types (or to the remote-sensing readers whose
-packages the image lacks).  Container-only: skipped where /root/reference is absent
-(the GPU box).  The YAMLs are read as data; no reference code is imported or run.
+packages the image lacks).  The YAMLs are read as data; no reference code is
+imported or run.
 
 Not covered: ``train_SwinIR_StyleCNN_*.yml`` name ``SwinIR_StyleCNN``, an arch the reference itself
 does not define (no ``class SwinIR_StyleCNN`` anywhere under basicsr/); ``train_SwinIR_L2S288_scratch.yml``
@@ -18,8 +19,7 @@ import os
 import pytest
 import torch
 
-REF = '/root/reference/options'
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason='reference option files not present')
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_options')
 
 PATTERNS = ['train/EDSR/*.yml', 'train/RCAN/*.yml', 'train/SwinIR/train_SwinIR_S[R2]*.yml',
             'train/ESRGAN/train_RRDBNet_PSNR_x4.yml', 'train/SRResNet_SRGAN/train_MSRResNet_x*.yml', 'test/EDSR/*.yml',
@@ -38,7 +38,7 @@ def _files():
     return [os.path.relpath(f, REF) for f in out]
 
 
-@pytest.mark.parametrize('rel', _files() if os.path.isdir(REF) else ['none'])
+@pytest.mark.parametrize('rel', _files())
 def test_reference_yaml_parses_and_builds(rel, tmp_path):
     import basicsr4rs_amd.archs  # noqa: F401
     import basicsr4rs_amd.data  # noqa: F401

@@ -10,7 +10,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q -x --timeout 300 --timeout
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1 \
   && tail -2 $OUT/smoke.log || { tail -20 $OUT/smoke.log; exit 1; }
 for wl in edsr rcan swinir rrdb; do
-  timeout -k 10 400 python -u bench.py --workload $wl > $OUT/bench_$wl.log 2>&1 || { tail -20 $OUT/bench_$wl.log; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --workload $wl > $OUT/bench_$wl.log 2>&1 || { tail -20 $OUT/bench_$wl.log; exit 1; }
   grep '^{"metric' $OUT/bench_$wl.log > $OUT/bench_$wl.json
   python3 -c "import json; d=json.load(open('$OUT/bench_$wl.json')); r=d['roofline']; print('$wl', d['ms_per_step'], d['value'], r['kernel'], r['frac'], d['cpu_baseline']['value'] if d.get('cpu_baseline') else None)"
 done

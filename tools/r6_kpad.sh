@@ -7,7 +7,7 @@ OUT=gpurun_out/${1:-kpad}; mkdir -p $OUT
 for r in $(seq ${ROUNDS:-2}); do
   for v in unset 0; do
     if [ $v = unset ]; then unset SR_CONV_KPAD; else export SR_CONV_KPAD=$v; fi
-    timeout -k 10 300 python -u bench.py --workload swinir --no-cpu-baseline > $OUT/full_${v}_$r.log 2>&1 || exit 1
+    timeout -k 10 300 python -u bench.py --full --workload swinir --no-cpu-baseline > $OUT/full_${v}_$r.log 2>&1 || exit 1
     timeout -k 10 300 python -u bench.py --workload swinir --no-cpu-baseline --no-trace --no-parity > $OUT/notrace_${v}_$r.log 2>&1 || exit 1
     python3 -c "
 import json

@@ -7,7 +7,7 @@ timeout -k 10 300 python -u -m pytest tests/test_conv_gpu.py tests/test_workload
   --timeout 200 --timeout-method thread -p no:cacheprovider -k "kpad or swinir or swin" > $OUT/tests.log 2>&1 || { tail -30 $OUT/tests.log; exit 1; }
 tail -1 $OUT/tests.log
 for r in 1 2 3; do
-  timeout -k 10 780 python -u bench.py > $OUT/bench_$r.log 2> $OUT/bench_$r.err || { tail -20 $OUT/bench_$r.err; exit 1; }
+  timeout -k 10 780 python -u bench.py --full > $OUT/bench_$r.log 2> $OUT/bench_$r.err || { tail -20 $OUT/bench_$r.err; exit 1; }
   grep '^{"metric' $OUT/bench_$r.log > $OUT/bench_$r.json
   python3 -c "
 import json; d=json.load(open('$OUT/bench_$r.json'))

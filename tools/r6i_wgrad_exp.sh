@@ -6,4 +6,5 @@ for r in 1 2; do for L in E0 E3 E4; do
   SR_HIP_LIB=abl/lib$L.so timeout -k 10 300 python -u bench.py --workload edsr --no-cpu-baseline --no-parity --no-trace --steps 20 --warmup 5 > gpurun_out/r6i/edsr_$L.json 2>/dev/null || exit 1
   python3 -c "import json; d=json.loads(open('gpurun_out/r6i/edsr_$L.json').read().strip().splitlines()[-1]); print('edsr $L', d['ms_per_step'])"
 done; done > gpurun_out/r6i/step.log
-timeout -k 10 600 python -u bench.py --lr-px 256 --batch 2 --steps 10 --warmup 3 --sub-workloads swinir --sub-cpu-seconds 8 --cpu-seconds 8 > gpurun_out/r6i/sweep.json 2> gpurun_out/r6i/sweep.err
+SWEEP=${SWEEP_OUT:-build/r6i}; mkdir -p $SWEEP
+timeout -k 10 600 python -u bench.py --full --lr-px 256 --batch 2 --steps 10 --warmup 3 --sub-workloads swinir --sub-cpu-seconds 8 --cpu-seconds 8 > $SWEEP/sweep.json 2> $SWEEP/sweep.err
