@@ -15,6 +15,7 @@
 // same 16-byte chunk image.  The epilogue stages the fp32 tile through LDS and applies
 // bias, activation, ReLU-mask gate, scale, residual, pixel-shuffle / NCHW store with
 // 16-byte coalesced stores.
+#include <atomic>
 #include <cstdlib>
 #include <utility>
 #include <type_traits>
@@ -903,9 +904,37 @@ struct PphGeom {
 // own pieces hold; zeros at the image edges; the other waves a zero dummy, so every halo issue is two
 // ops per wave and the retire point counts 8 instead of 6), and the epilogue maps tile rows to pixels
 // (FwdArgs.strip64)
-template <int R, int P2 = 0, bool STRIP = false>
+// PERS (R 4, P2 2, no strips; tiles_n 1, plain NHWC in / out, at most one gate-or-residual operand): the
+// persistent multi-tile form.  The grid is min(tiles, G) blocks and block b owns a contiguous run of
+// tiles (vertical neighbours in an image, so two of the next tile's six halo rows are L2 hits); ONE K
+// loop runs across the run: the ring's chunk counter and the B double buffer's parity carry on over the
+// tile boundary, so the next tile's chunk 0 is streamed as "chunk nchunk" of this one (its own image / row)
+// and its B(0) / B(1) as B(nk) / B(nk+1); the per-step issue counts and the counted waits are unchanged.
+// Only the first tile of a block pays the cold prologue (and the dispatch, LDS zeroing, address setup).
+// At loop end the LDS holds the next tile's six rows and two B tiles; the five slots after them are free
+// and four of them stage the accumulators in eight passes of 32 tile rows -- 16 of each wave row, so all
+// eight waves write -- (a slot is exactly 8 rows of CSTR floats; the run of slots may wrap; their zero
+// border columns are rewritten afterwards).  The tile's gate / residual operand (16 x 16 B per thread) and bias are loaded in two batches of 8, the
+// first issued before the K loop's last barrier, the second during pass 1 (in flight under passes 2-3),
+// instead of four serialized batches each waited for at once.  Per element the arithmetic and its order are
+// epilogue_tile's, so the outputs are bitwise those of the one-tile form.  Nothing depends on dispatch
+// order or residency: no inter-block communication.
+template <int R, int P2 = 0, bool STRIP = false, bool PERS = false>
 __global__ __launch_bounds__(512) void conv3x3_fwd_pph_kernel(FwdArgs a) {
   static_assert(!STRIP || (R == 4 && P2 == 2), "pph strips: the R 4 two-interval form");
+  static_assert(!PERS || (R == 4 && P2 == 2 && !STRIP), "pph persistent: the R 4 two-interval form");
+#ifdef SR_BAND_STAMPS
+  // wave 0's phase clocks (tools/pph_stamps.py): [0] entry, [1] tiles, then per tile (the first three)
+  // K loop start, K loop end, end of the first / second half of the epilogue; [14] cycles waiting for the
+  // epilogue operand (PERS).  One lane stores each value as it is taken (plain vector stores).
+  const unsigned long long st_entry = __builtin_readcyclecounter();
+  // (the buffer holds 4096 blocks x 16 values)
+  unsigned long long* const st_p =
+      a.stamps && threadIdx.x == 0 && blockIdx.x < 4096 ? a.stamps + (size_t)blockIdx.x * 16 : nullptr;
+  auto stamp = [&](int ti, int k) {
+    if (st_p && ti < 3) st_p[2 + 4 * ti + k] = __builtin_readcyclecounter();
+  };
+#endif
   using G = PphGeom<R>;
   constexpr int W = G::W, RH = R + 2;
   constexpr int CSTR = 256 + 4;
@@ -1072,6 +1101,256 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_pph_kernel(FwdArgs a) {
     __builtin_amdgcn_s_setprio(0);
   };
 
+  if constexpr (PERS) {
+    constexpr int NS = G::NSLOT;
+    const int nb = (int)gridDim.x, run = (int)tile;  // the run index (XCD-remapped block)
+    const int tq = a.tiles / nb, trem = a.tiles - tq * nb;
+    int tl = run * tq + (run < trem ? run : trem);  // the first trem runs own one tile more
+    const int tend = tl + tq + (run < trem ? 1 : 0);
+    const int HW = a.H * W;
+    auto tile_pos = [&](int t_, int& im, int& yy) {
+      const int m = t_ * 256;
+      im = m / HW;
+      yy = (m - im * HW) / W;
+    };
+    int timg, ty0;
+    tile_pos(tl, timg, ty0);
+    auto issue_row_p = [&](int slot, int lc, int rr, int im, int yy0) {  // row rr of chunk lc of a tile
+      const int y = yy0 - 1 + rr;
+      glds16(xr, smem + PPH_SLOT0 + slot * G::ROWB + 128 + w * 1024,
+             (unsigned)y < (unsigned)a.H ? (uint32_t)(im * a.H + y) * rowb + hlane + (uint32_t)lc * 128u : SR_OOB);
+    };
+    auto lds_sync = [&]() {  // LDS writes / reads of this wave done, then the block barrier
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      pp_barrier();
+    };
+    // the epilogue operand: the ReLU / GELU' gate or the residual (the dispatch admits one of them)
+    const bool useg = a.gate != nullptr;
+    const __amdgpu_buffer_rsrc_t orr = useg ? make_rsrc(a.gate, a.g_bytes) : make_rsrc(a.res, a.r_bytes);
+    // this thread's 8 channels; its 16 groups, in the order the passes consume them: group q is tile row
+    // e_r0 + e_row(q)
+    const int e_cg = tid & 31, e_n = e_cg * 8, e_r0 = tid >> 5;
+    auto e_row = [](int q) { return (q >> 3) * 128 + (q & 1) * 64 + ((q >> 1) & 3) * 16; };
+    // (Cout is 256: every channel group of the tile is stored.)  Without an operand the loads read nothing
+    const bool e_oval = useg || (a.res && e_n < a.rcols);
+    const uint32_t e_ostep = (uint32_t)(useg ? a.ldg : a.ldr) * 2u;  // bytes per operand row
+
+    // cold prologue (first tile only): the six rows of chunk 0, B(0), B(1)
+#pragma unroll 1
+    for (int rr = 0; rr < 6; ++rr) issue_row_p(rr, 0, rr, timg, ty0);
+    issue_b(0, 0, 0, 0);
+    issue_b(0, 0, 0, 1);
+    issue_b(1, 0, 1, 0);
+    issue_b(1, 0, 1, 1);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    pp_barrier();
+    if (wr) pp_barrier();  // stagger: waves 4-7 run one barrier behind
+
+    int s0 = 0;   // slot of row 0 of the current chunk: (6 * chunks so far) mod NS
+    int par = 0;  // B buffer of the current step: (steps so far) & 1
+    int m0t = tl * 256;
+#ifdef SR_BAND_STAMPS
+    int sti = 0;
+    if (st_p) { st_p[0] = st_entry; st_p[1] = (unsigned long long)(tend - tl); }
+#endif
+#pragma unroll 1
+    for (; tl < tend; ++tl) {
+      const bool has_next = tl + 1 < tend;
+      int nimg = timg, ny0 = ty0;
+      if (has_next) tile_pos(tl + 1, nimg, ny0);
+#ifdef SR_BAND_STAMPS
+      stamp(sti, 0);
+#endif
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[h][g][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      int cc = 0, tap = 0;      // this step
+      int n2cc = 0, n2tap = 2;  // the step after the next; past this tile's nk steps, the next tile's first two
+#pragma unroll 1
+      for (int t = 0; t < nk; ++t) {
+        const int buf = par;
+        par ^= 1;
+        const int ty = tap / 3, tx = tap - ty * 3;
+        int sa = s0 + ty + wr;
+        if (sa >= NS) sa -= NS;
+        int sb = sa + 2;
+        if (sb >= NS) sb -= NS;
+        // R1
+        read_a(sa, tx);
+        read_b(buf, 0);
+        read_b(buf, 1);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        pp_barrier();
+        mma(0, 0);
+        mma(0, 1);
+        pp_barrier();
+        // R2: B(t+2) -- of the next tile in the last two steps --, then the halo piece: row `tap` of the
+        // next chunk, which after the last chunk is chunk 0 of the next tile
+        read_a(sb, tx);
+        if (t + 2 < nk || has_next) { issue_b(buf, n2cc, n2tap, 0); issue_b(buf, n2cc, n2tap, 1); }
+        else { issue_b_dummy(); issue_b_dummy(); }
+        {
+          const bool lastc = cc + 1 == nchunk;
+          if (tap < 6 && (!lastc || has_next)) {
+            int sl = s0 + 6 + tap;
+            if (sl >= NS) sl -= NS;
+            issue_row_p(sl, lastc ? 0 : cc + 1, tap, lastc ? nimg : timg, lastc ? ny0 : ty0);
+          } else {
+            issue_dummy();
+          }
+        }
+        if (wr) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        pp_barrier();
+        mma(1, 1);
+        mma(1, 0);
+        if (!wr) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        pp_barrier();
+        if (++tap == 9) {
+          tap = 0;
+          ++cc;
+          s0 += 6;
+          if (s0 >= NS) s0 -= NS;
+        }
+        if (++n2tap == 9) {
+          n2tap = 0;
+          if (++n2cc == nchunk) n2cc = 0;
+        }
+      }
+      // the tile's operand and bias in flight while the accumulators are staged: the first half's 8
+      // groups now, the second half's after pass 1 (into the registers of the accumulators staged by then)
+      u32x4 ova[8], ovb[8];
+      const uint32_t ob =
+          (uint32_t)(((size_t)(m0t + e_r0) * (useg ? a.ldg : a.ldr) + (useg ? a.gcoff : a.rcoff) + e_n) * 2);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) ova[q] = buf_load16(orr, e_oval ? ob + (uint32_t)e_row(q) * e_ostep : SR_OOB);
+      f32x4 bias0 = f32x4{0.f, 0.f, 0.f, 0.f}, bias1 = bias0;
+      if (a.bias) {
+        bias0 = *(const f32x4*)(a.bias + e_n);
+        bias1 = *(const f32x4*)(a.bias + e_n + 4);
+      }
+      if (!wr) pp_barrier();  // balance the stagger: every wave is past its last MFMA and LDS read
+#ifdef SR_BAND_STAMPS
+      stamp(sti, 1);
+#endif
+      // s0 is now the slot of row 0 of the NEXT chunk: rows s0 .. s0+5 (mod NS) are the next tile's, slots
+      // s0+6 .. s0+9 stage 8 tile rows each.  Pass p = (h, i) stages accumulator row group i of half h of
+      // every wave: 16 tile rows of each wave row wr (staging rows 16 wr .. 16 wr + 15), so all 8 waves write
+#pragma unroll
+      for (int p = 0; p < 8; ++p) {
+        const int h = p >> 2, i = p & 3;  // tile rows 128 h + 64 wr + 16 i .. + 15
+        if (p) lds_sync();
+        {
+          int sl = s0 + 6 + wr * 2 + (lane >> 5);
+          if (sl >= NS) sl -= NS;
+          float* Cw = (float*)(smem + PPH_SLOT0 + sl * G::ROWB) + (((lane >> 4) & 1) * 4) * CSTR + wc * 32 + (lane & 15);
+#pragma unroll
+          for (int g = 0; g < 2; ++g)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) Cw[r * CSTR + g * 128 + j * 16] = acc[h][g][i][j][r];
+        }
+        lds_sync();
+        if (p == 0) {
+#ifdef SR_BAND_STAMPS
+          const unsigned long long tw0 = __builtin_readcyclecounter();
+#endif
+          // the operand batch, and with it every older DMA of this wave (the next tile's rows and B
+          // tiles: the barrier of pass 1 makes them visible to the block)
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#ifdef SR_BAND_STAMPS
+          if (st_p && sti < 3) st_p[14] += __builtin_readcyclecounter() - tw0;
+#endif
+        }
+#pragma unroll
+        for (int k2 = 0; k2 < 2; ++k2) {
+          const int q = p * 2 + k2;
+          int sl = s0 + 6 + k2 * 2 + (tid >> 8);
+          if (sl >= NS) sl -= NS;
+          const float* Cr = (const float*)(smem + PPH_SLOT0 + sl * G::ROWB) + (e_r0 & 7) * CSTR + e_cg * 8;
+          {
+            const int m = m0t + e_r0 + e_row(q);
+            float v[8];
+            const f32x4 c0 = *(const f32x4*)Cr;
+            const f32x4 c1 = *(const f32x4*)(Cr + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { v[j] = c0[j]; v[4 + j] = c1[j]; }
+            if (a.bias) {
+#pragma unroll
+              for (int j = 0; j < 4; ++j) { v[j] += bias0[j]; v[4 + j] += bias1[j]; }
+            }
+            act_apply_n(v, a.act, a.slope);
+            // the operand group is consumed HERE on every path (also when no operand is applied), so the
+            // compiler's own wait for it is placed here and no load is left pending into the next tile
+            // (a pending one makes it drain vmcnt -- the output stores -- where its register is reused)
+            u32x4 ovq = q < 8 ? ova[q & 7] : ovb[q & 7];
+            asm volatile("" : "+v"(ovq));
+            float o8[8];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const uint32_t oq = ovq[j];
+              o8[2 * j] = bf16_to_f32(oq & 0xffff);
+              o8[2 * j + 1] = bf16_to_f32(oq >> 16);
+            }
+            if (useg) {
+              if (a.gate_mode == 1) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] *= o8[j];
+              } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] *= (o8[j] > 0.f ? 1.f : a.gate_slope);
+              }
+            }
+            {
+              const float al = a.alpha;
+#pragma unroll
+              for (int j = 0; j < 8; ++j) v[j] *= al;
+            }
+            if (!useg && a.res && e_n < a.rcols) {
+#pragma unroll
+              for (int j = 0; j < 8; ++j) v[j] = a.beta * o8[j] + v[j];
+            }
+            u32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = pack_bf16x2(v[2 * j], v[2 * j + 1]);
+            *(u32x4*)((bf16_t*)a.y + ((size_t)m * a.ldy + a.ycoff + e_n)) = o;
+          }
+        }
+        if (p == 1) {
+#pragma unroll
+          for (int q = 0; q < 8; ++q) ovb[q] = buf_load16(orr, e_oval ? ob + (uint32_t)e_row(8 + q) * e_ostep : SR_OOB);
+        }
+#ifdef SR_BAND_STAMPS
+        if (p == 3) stamp(sti, 2);
+        if (p == 7) stamp(sti, 3);
+#endif
+      }
+#ifdef SR_BAND_STAMPS
+      ++sti;
+#endif
+      if (has_next) {
+        lds_sync();  // the last pass's reads are done: rewrite the staging slots' zero border columns
+        if (tid < 64) {
+          int sl = s0 + 6 + (tid >> 4);
+          if (sl >= NS) sl -= NS;
+          const int e = tid & 15;
+          *(u32x4*)(smem + PPH_SLOT0 + sl * G::ROWB + (e < 8 ? 0 : (W + 1) * 128) + (e & 7) * 16) = u32x4{0u, 0u, 0u, 0u};
+        }
+        m0t += 256;
+        timg = nimg;
+        ty0 = ny0;
+        pp_barrier();
+        if (wr) pp_barrier();  // stagger again
+      }
+    }
+    return;
+  }
+
   // prologue: the rows chunk 0 needs first (R = 4: all six; R = 2: rows 0-2, row 3 follows
   // at taps 0-1) and both B halves of step 0, all landed
 #pragma unroll 1
@@ -1085,6 +1364,10 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_pph_kernel(FwdArgs a) {
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   pp_barrier();
+#ifdef SR_BAND_STAMPS
+  if (st_p) { st_p[0] = st_entry; st_p[1] = 1; }
+  stamp(0, 0);
+#endif
   if (wr) pp_barrier();  // stagger: waves 4-7 run one barrier behind
 
   int cc = 0, tap = 0;   // this step
@@ -1197,6 +1480,9 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_pph_kernel(FwdArgs a) {
   }
   if (!wr) pp_barrier();  // balance the stagger
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#ifdef SR_BAND_STAMPS
+  stamp(0, 1);
+#endif
 
   float* Cs = (float*)smem;
 #pragma unroll
@@ -1214,6 +1500,9 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_pph_kernel(FwdArgs a) {
                 acc[h][g][i][j][r];
     __syncthreads();
     epilogue_tile<bf16_t, 128, 256, 512>(a, Cs, CSTR, m0 + h * 128, n0, tid);
+#ifdef SR_BAND_STAMPS
+    stamp(0, 2 + h);
+#endif
   }
 }
 
@@ -4710,11 +4999,38 @@ bool fwd_use_pph(const FwdArgs& a) {
          (a.in_ps == 0 || (a.fd_cps.d % 64 == 0 && g_variant != 50)) && a.in_up == 1 && a.tap0 == 0;
 }
 
+// Compute units of the current device, queried once per device (the persistent pph grid)
+int device_cus() {
+  static std::atomic<int> cus[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  int n = cus[dev].load(std::memory_order_relaxed);
+  if (n <= 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+// Grid of the persistent multi-tile form of the pph kernel (conv3x3_fwd_pph_kernel<4, 2, false, true>), 0:
+// the one-tile form.  W 64 whole-row tiles (fwd_use_pph), Cout 256 (one full column tile), plain NHWC input and output,
+// bias / activation / alpha and at most ONE of gate (modes 0, 1) and residual -- the EDSR / RCAN-style
+// body convs and their dgrads -- and more tiles than G blocks (with one tile per block the form is the
+// one-tile form).  G: the device's CU count, or knob SR_PPH_GRID (tests: several tiles per block at
+// small shapes).  Variant 80: the one-tile form for them (A/B, tests).
+int pph_pers_grid(const FwdArgs& a) {
+  if (g_variant == 80 || a.W != 64 || a.Cout != 256 || a.tiles_n != 1 || a.in_ps != 0 || a.out_ps != 0 || a.colsum || a.out_nchw ||
+      a.aux || a.res2 || a.row_scale || a.dot || (a.gate && a.res) || (a.gate && a.gate_mode == 2) || a.M % 256)
+    return 0;
+  const int G = sr_knob(K_PPH_GRID) > 0 ? sr_knob(K_PPH_GRID) : device_cus();
+  return a.tiles > G ? G : 0;
+}
+
 hipError_t launch_fwd_big(const FwdArgs& a0, hipStream_t s) {
   FwdArgs a = a0;
   const int tm = (a.M + 255) / 256;
   a.tiles_n = (a.Cout + 255) / 256;
   a.tiles = tm * a.tiles_n;
+  a.stamps = g_sr_stamps;
   if (g_variant == 2)
     hipLaunchKernelGGL(conv3x3_fwd_big_kernel, dim3(a.tiles), dim3(512), 0, s, a);
   else if (fwd_use_pph_strip(a)) {
@@ -4727,6 +5043,8 @@ hipError_t launch_fwd_big(const FwdArgs& a0, hipStream_t s) {
     hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<2, 0>), dim3(a.tiles), dim3(512), 0, s, a);
   else if (g_variant != 59 && fwd_use_pph(a))
     if (g_variant == 61) hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<4, 1>), dim3(a.tiles), dim3(512), 0, s, a);
+    else if (const int gp = pph_pers_grid(a))
+      hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<4, 2, false, true>), dim3(gp), dim3(512), 0, s, a);
     else hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<4, 2>), dim3(a.tiles), dim3(512), 0, s, a);
   else if (fwd_use_pph(a))
     hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<4, 0>), dim3(a.tiles), dim3(512), 0, s, a);
@@ -5568,10 +5886,10 @@ const char* sr_conv3x3_wgrad_kernel_name(const sr_conv3x3_wgrad_desc* d) {
 
 // Kernel-variant switch for the parity tests' cross-checks: 0 = automatic, 1 = never a 256x256 kernel,
 // 2 = the two-barrier 256x256 kernels; the others each route one family to the kernel it replaced
-// (24, 28, 29, 33, 34, 35, 36, 37, 50, 55, 59, 61, 62, 63, 64, 67, 68, 76, 77, 78, 79: see their sites above).  The
+// (24, 28, 29, 33, 34, 35, 36, 37, 50, 55, 59, 61, 62, 63, 64, 67, 68, 76, 77, 78, 79, 80: see their sites above).  The
 // measured-slower paths and the timing ablations were removed in round 6 (git history).
 int sr_conv3x3_set_variant(int variant) {
-  static const int kValid[] = {0, 1, 2, 24, 28, 29, 33, 34, 35, 36, 37, 50, 55, 59, 61, 62, 63, 64, 67, 68, 76, 77, 78, 79};
+  static const int kValid[] = {0, 1, 2, 24, 28, 29, 33, 34, 35, 36, 37, 50, 55, 59, 61, 62, 63, 64, 67, 68, 76, 77, 78, 79, 80};
   bool ok = false;
   for (int v : kValid) ok = ok || v == variant;
   if (!ok) return sr_fail(SR_EINVAL, "conv3x3_set_variant: not a parity cross-check variant");

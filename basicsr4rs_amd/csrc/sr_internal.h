@@ -24,6 +24,7 @@ enum SrKnob {
   K_DCN_GX_FX,      // SR_DCN_GX_FX: 32 / 64-bit fixed-point scatter image
   K_SWIN_ATTN_DBG,  // SR_SWIN_ATTN_DBG: fused attention timing ablations (wrong results)
   K_WG_ROW3,        // SR_WG_ROW3: 0 = the kernel-row wgrad off (pp kernel), > 0 = its bias-role group size
+  K_PPH_GRID,       // SR_PPH_GRID: blocks of the persistent pph forward grid (default: the CU count)
   K_COUNT
 };
 int sr_knob(SrKnob k);
