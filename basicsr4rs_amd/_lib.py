@@ -46,6 +46,11 @@ class PrepItem(ctypes.Structure):
                 ('bias_g', _vp)]
 
 
+class ConvKDesc(ctypes.Structure):
+    _fields_ = [('dtype', _i), ('N', _i), ('H', _i), ('W', _i), ('k', _i), ('Cin', _i), ('Cin_real', _i), ('Cout', _i),
+                ('Cout_real', _i), ('act', _i), ('alpha', _f), ('scale', _f), ('accumulate', _i)]
+
+
 class DcnDesc(ctypes.Structure):
     _fields_ = [('dtype', _i), ('N', _i), ('C', _i), ('H', _i), ('W', _i), ('Cp', _i), ('Ho', _i), ('Wo', _i),
                 ('kh', _i), ('kw', _i), ('stride_h', _i), ('stride_w', _i), ('pad_h', _i), ('pad_w', _i),
@@ -75,6 +80,10 @@ SIGNATURES = {
     'sr_conv_prep_batch': (_i, [_i, _vp, _vp, _i, _i, _vp]),
     'sr_conv3x3_prep': (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'sr_conv_prep_mapped': (_i, [_i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sr_convk_fwd': (_i, [ctypes.POINTER(ConvKDesc), _vp, _vp, _vp, _vp, _vp]),
+    'sr_convk_wgrad_workspace': (_sz, [ctypes.POINTER(ConvKDesc)]),
+    'sr_convk_wgrad': (_i, [ctypes.POINTER(ConvKDesc), _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    'sr_bicubic_up': (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'sr_nchw_to_nhwc': (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'sr_nhwc_to_nchw': (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'sr_pixel_shuffle_nchw': (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

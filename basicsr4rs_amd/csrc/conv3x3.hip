@@ -4894,7 +4894,8 @@ __global__ __launch_bounds__(256) void prep_batch_kernel(const sr_prep_item* __r
     if (block_start[mid] <= b) lo = mid; else hi = mid - 1;
   }
   const sr_prep_item it = items[lo];
-  const int taps = it.ksize == 1 ? 1 : 9;
+  // ksize 5 / 7 / 9 (the k x k convs of convk.hip): the tile goes through LDS nine taps at a time
+  const int taps_all = it.ksize == 1 ? 1 : (it.ksize > 3 ? it.ksize * it.ksize : 9);
   const int tci = (it.Cin + PREP_T - 1) / PREP_T;
   const int t = b - block_start[lo];
   const int n0 = (t / tci) * PREP_T, c0 = (t % tci) * PREP_T;
@@ -4905,19 +4906,6 @@ __global__ __launch_bounds__(256) void prep_batch_kernel(const sr_prep_item* __r
     if (nn >= it.Cout_real) return -1;
     return it.out_ps > 0 ? (nn % cps) * r2 + nn / cps : nn;
   };
-  const int per = PREP_T * taps;  // elements per GEMM row of the tile
-  for (int idx = tid; idx < PREP_T * per; idx += 256) {
-    const int nl = idx / per, rem = idx - nl * per;
-    const int cil = rem / taps, tap = rem - cil * taps;
-    const int nn = n0 + nl, ci = c0 + cil;
-    float v = 0.f;
-    if (nn < it.Cout && ci < it.Cin) {
-      const int co = row_of(nn);
-      const int cs = it.col_map ? it.col_map[ci] : (ci < it.Cin_real ? ci : -1);
-      if (co >= 0 && cs >= 0) v = it.w[((size_t)co * it.Cin_real + cs) * taps + tap];
-    }
-    tile[nl][tap][cil] = v;
-  }
   if (it.bias_g && c0 == 0 && tid < PREP_T) {
     const int nn = n0 + tid;
     if (nn < it.Cout) {
@@ -4925,52 +4913,72 @@ __global__ __launch_bounds__(256) void prep_batch_kernel(const sr_prep_item* __r
       it.bias_g[nn] = (co >= 0 && it.bias) ? it.bias[co] : 0.f;
     }
   }
-  __syncthreads();
   T* wf = (T*)it.wf;
   T* wd = (T*)it.wd;
-  if (Elt<T>::SIZE == 2 && it.Cin % 8 == 0 && it.Cout % 8 == 0) {
-    // bf16: 8 consecutive GEMM-row elements per thread, one 16-B store (with Cin and Cout multiples of
-    // 8 and the tile origins of 32, an 8-run lies wholly inside or outside the image; a pixel-shuffled
-    // conv's Cout -- 27 at x3 -- takes the element loop below); the 2-B stores of that loop ran at
-    // ~1.5 TB/s (EDSR: 227 us per step)
-    constexpr int G8 = PREP_T / 8;
-    for (int g = tid; g < PREP_T * taps * G8; g += 256) {
-      const int a0 = g / (taps * G8), r = g - a0 * (taps * G8);
-      const int tap = r / G8, e8 = (r - tap * G8) * 8;
-      if (wf) {  // wf[n][tap][ci]: n = n0 + a0, ci = c0 + e8 ..
-        const int nn = n0 + a0, ci = c0 + e8;
-        if (nn < it.Cout && ci < it.Cin) {
-          u32x4 o;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) o[j] = pack_bf16x2(tile[a0][tap][e8 + 2 * j], tile[a0][tap][e8 + 2 * j + 1]);
-          *(u32x4*)(wf + (size_t)nn * taps * it.Cin + (size_t)tap * it.Cin + ci) = o;
-        }
-      }
-      if (wd) {  // wd[ci][taps - 1 - tap][n]: ci = c0 + a0, n = n0 + e8 ..
-        const int ci = c0 + a0, nn = n0 + e8;
-        if (nn < it.Cout && ci < it.Cin) {
-          u32x4 o;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) o[j] = pack_bf16x2(tile[e8 + 2 * j][tap][a0], tile[e8 + 2 * j + 1][tap][a0]);
-          *(u32x4*)(wd + (size_t)ci * taps * it.Cout + (size_t)(taps - 1 - tap) * it.Cout + nn) = o;
-        }
-      }
-    }
-    return;
-  }
-  for (int idx = tid; idx < PREP_T * per; idx += 256) {
-    if (wf) {  // wf[n][tap][ci]: runs along ci
+  for (int t0 = 0; t0 < taps_all; t0 += 9) {
+    const int taps = taps_all - t0 < 9 ? taps_all - t0 : 9;  // taps t0 .. t0 + taps - 1 this pass
+    if (t0) __syncthreads();
+    const int per = PREP_T * taps;  // elements per GEMM row of the tile
+    for (int idx = tid; idx < PREP_T * per; idx += 256) {
       const int nl = idx / per, rem = idx - nl * per;
-      const int tap = rem / PREP_T, cil = rem - tap * PREP_T;
+      const int cil = rem / taps, tap = rem - cil * taps;
       const int nn = n0 + nl, ci = c0 + cil;
-      if (nn < it.Cout && ci < it.Cin) wf[(size_t)nn * taps * it.Cin + (size_t)tap * it.Cin + ci] = Elt<T>::from_f(tile[nl][tap][cil]);
+      float v = 0.f;
+      if (nn < it.Cout && ci < it.Cin) {
+        const int co = row_of(nn);
+        const int cs = it.col_map ? it.col_map[ci] : (ci < it.Cin_real ? ci : -1);
+        if (co >= 0 && cs >= 0) v = it.w[((size_t)co * it.Cin_real + cs) * taps_all + t0 + tap];
+      }
+      tile[nl][tap][cil] = v;
     }
-    if (wd) {  // wd[ci][taps - 1 - tap][n]: runs along n
-      const int cil = idx / per, rem = idx - cil * per;
-      const int tap = rem / PREP_T, nl = rem - tap * PREP_T;
-      const int nn = n0 + nl, ci = c0 + cil;
-      if (nn < it.Cout && ci < it.Cin)
-        wd[(size_t)ci * taps * it.Cout + (size_t)(taps - 1 - tap) * it.Cout + nn] = Elt<T>::from_f(tile[nl][tap][cil]);
+    __syncthreads();
+    if (Elt<T>::SIZE == 2 && it.Cin % 8 == 0 && it.Cout % 8 == 0) {
+      // bf16: 8 consecutive GEMM-row elements per thread, one 16-B store (with Cin and Cout multiples of
+      // 8 and the tile origins of 32, an 8-run lies wholly inside or outside the image; a pixel-shuffled
+      // conv's Cout -- 27 at x3 -- takes the element loop below); the 2-B stores of that loop ran at
+      // ~1.5 TB/s (EDSR: 227 us per step)
+      constexpr int G8 = PREP_T / 8;
+      for (int g = tid; g < PREP_T * taps * G8; g += 256) {
+        const int a0 = g / (taps * G8), r = g - a0 * (taps * G8);
+        const int tap = r / G8, e8 = (r - tap * G8) * 8;
+        const int gt = t0 + tap;
+        if (wf) {  // wf[n][tap][ci]: n = n0 + a0, ci = c0 + e8 ..
+          const int nn = n0 + a0, ci = c0 + e8;
+          if (nn < it.Cout && ci < it.Cin) {
+            u32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = pack_bf16x2(tile[a0][tap][e8 + 2 * j], tile[a0][tap][e8 + 2 * j + 1]);
+            *(u32x4*)(wf + (size_t)nn * taps_all * it.Cin + (size_t)gt * it.Cin + ci) = o;
+          }
+        }
+        if (wd) {  // wd[ci][taps - 1 - tap][n]: ci = c0 + a0, n = n0 + e8 ..
+          const int ci = c0 + a0, nn = n0 + e8;
+          if (nn < it.Cout && ci < it.Cin) {
+            u32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = pack_bf16x2(tile[e8 + 2 * j][tap][a0], tile[e8 + 2 * j + 1][tap][a0]);
+            *(u32x4*)(wd + (size_t)ci * taps_all * it.Cout + (size_t)(taps_all - 1 - gt) * it.Cout + nn) = o;
+          }
+        }
+      }
+      continue;
+    }
+    for (int idx = tid; idx < PREP_T * per; idx += 256) {
+      if (wf) {  // wf[n][tap][ci]: runs along ci
+        const int nl = idx / per, rem = idx - nl * per;
+        const int tap = rem / PREP_T, cil = rem - tap * PREP_T;
+        const int nn = n0 + nl, ci = c0 + cil;
+        if (nn < it.Cout && ci < it.Cin)
+          wf[(size_t)nn * taps_all * it.Cin + (size_t)(t0 + tap) * it.Cin + ci] = Elt<T>::from_f(tile[nl][tap][cil]);
+      }
+      if (wd) {  // wd[ci][taps - 1 - tap][n]: runs along n
+        const int cil = idx / per, rem = idx - cil * per;
+        const int tap = rem / PREP_T, nl = rem - tap * PREP_T;
+        const int nn = n0 + nl, ci = c0 + cil;
+        if (nn < it.Cout && ci < it.Cin)
+          wd[(size_t)ci * taps_all * it.Cout + (size_t)(taps_all - 1 - t0 - tap) * it.Cout + nn] =
+              Elt<T>::from_f(tile[nl][tap][cil]);
+      }
     }
   }
 }
@@ -6086,11 +6094,12 @@ int sr_conv_prep_mapped(int dtype, int ksize, const float* w, const float* bias,
                         int Cout, int Cin, int out_ps, const int* row_map, const int* col_map, void* wf, void* wd,
                         float* bias_g, void* stream) {
   if (!w) return sr_fail(SR_EINVAL, "conv_prep: null weight");
-  if (ksize != 1 && ksize != 3) return sr_fail(SR_EINVAL, "conv_prep: ksize must be 1 or 3");
+  if (ksize != 1 && ksize != 3 && ksize != 5 && ksize != 7 && ksize != 9)
+    return sr_fail(SR_EINVAL, "conv_prep: ksize must be 1, 3, 5, 7 or 9");
   if ((!row_map && Cout < Cout_real) || (!col_map && Cin < Cin_real)) return sr_fail(SR_EINVAL, "conv_prep: padded < real");
   if (out_ps > 0 && (Cout_real % (out_ps * out_ps) || Cout != Cout_real || row_map))
     return sr_fail(SR_EINVAL, "conv_prep: shuffled conv needs Cout == Cout_real divisible by r^2");
-  const int taps = ksize == 1 ? 1 : 9;
+  const int taps = ksize * ksize;
   const int64_t total = (int64_t)Cout * Cin * taps;
   const int64_t work = total > Cout ? total : Cout;
   hipStream_t s = (hipStream_t)stream;

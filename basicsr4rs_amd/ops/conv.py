@@ -283,7 +283,7 @@ def prepared_images(weight, bias, dtype, shape, maps=(None, None), tag=''):
     cout_real, cin_real, cout_p, cin_p, out_ps, ksize = shape
     if e is None:
         dev = weight.device
-        taps = 9 if ksize == 3 else 1
+        taps = ksize * ksize if ksize >= 3 else 1  # 5 / 7 / 9: the k x k convs of ops/convk.py
         e = _Prep()
         e.weight, e.bias, e.dtype, e.shape, e.maps = weight, bias, dtype, shape, maps
         e.val = (torch.empty(cout_p, taps * cin_p, device=dev, dtype=dtype),

@@ -179,7 +179,7 @@ int sr_conv3x3_prep(int dtype, const float* w, const float* bias, int Cout_real,
                     int Cout, int Cin, int out_ps, void* wf, void* wd, float* bias_g,
                     void* stream);
 /* One conv / linear weight of a batched GEMM-image preparation (same meaning as the arguments
- * of sr_conv_prep_mapped; ksize 1 or 3). */
+ * of sr_conv_prep_mapped; ksize 1, 3, 5, 7 or 9). */
 typedef struct {
   const float* w;
   const float* bias;
@@ -197,12 +197,51 @@ int sr_conv_prep_blocks(const sr_prep_item* item);
  * Replaces the per-parameter re-preparation after every optimizer step. */
 int sr_conv_prep_batch(int dtype, const sr_prep_item* items, const int* block_start, int n, int total_blocks,
                        void* stream);
-/* General form: ksize 1 or 3; row_map[n] (n < Cout) = parameter row of GEMM column n or -1
+/* General form: ksize 1 or 3, or 5 / 7 / 9 for the k x k convs of sr_convk_fwd (taps = ksize^2,
+ * w[Cout_real][Cin_real][ksize][ksize], tap = ky*ksize + kx); row_map[n] (n < Cout) = parameter row of GEMM column n or -1
  * (zero row), col_map[k] (k < Cin) = parameter column of GEMM input channel k or -1; NULL maps
  * = identity (+ out_ps permutation).  nn.Linear weights are [out][in] = 1x1 conv weights. */
 int sr_conv_prep_mapped(int dtype, int ksize, const float* w, const float* bias, int Cout_real,
                         int Cin_real, int Cout, int Cin, int out_ps, const int* row_map,
                         const int* col_map, void* wf, void* wd, float* bias_g, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * k x k convolution for narrow channel counts (csrc/convk.hip): stride 1, zero padding k / 2,
+ * dilation 1, groups 1, odd k in {3, 5, 7, 9}, dense NHWC maps [N][H][W][C] of `dtype` with the
+ * padded channel counts Cin, Cout (multiples of 8, <= 64; padded channels of x are zero), any
+ * N, H, W >= 1.  SRCNN's 9x9 / 5x5 layers (nn.Conv2d(c, c', k, 1, k // 2)).  Anything outside
+ * this envelope returns SR_EINVAL before any launch.
+ *
+ * Forward:  y = alpha * act(conv(x, w) + bias), act SR_ACT_NONE / SR_ACT_RELU; channels
+ *   Cout_real .. Cout - 1 of y are stored as zeros.  w: [Cout][k*k*Cin] GEMM rows, K index =
+ *   tap*Cin + ci (tap = ky*k + kx): the wf image of sr_conv_prep_mapped with ksize = k; bias:
+ *   its bias_g, or NULL.  The input gradient is the same call on the wd image (Cin and Cout
+ *   swapped, no bias), after sr_act_backward for a ReLU layer.
+ * Weight gradient:  dw[co][ci][ky][kx] = scale * sum_p dy[p][co] * x[p + tap][ci], db[co] = scale *
+ *   sum_p dy[p][co] (fp32, nn.Conv2d parameter layout over the real channels; db may be NULL), from
+ *   fp32 partial slabs in a workspace of sr_convk_wgrad_workspace(d) bytes reduced in a fixed order
+ *   (deterministic, no atomics).  accumulate bit 0: dw += / db += in place (sr_conv3x3_wgrad's
+ *   convention).
+ * ------------------------------------------------------------------------------- */
+typedef struct sr_convk_desc {
+  int dtype;
+  int N, H, W;
+  int k;
+  int Cin, Cin_real;
+  int Cout, Cout_real;
+  int act;         /* forward */
+  float alpha;     /* forward */
+  float scale;     /* weight gradient */
+  int accumulate;  /* weight gradient */
+} sr_convk_desc;
+int sr_convk_fwd(const sr_convk_desc* d, const void* x, const void* w, const float* bias, void* y, void* stream);
+size_t sr_convk_wgrad_workspace(const sr_convk_desc* d);
+int sr_convk_wgrad(const sr_convk_desc* d, const void* dy, const void* x, void* workspace, size_t ws_bytes, float* dw,
+                   float* db, void* stream);
+/* Bicubic upsampling by an integer scale s >= 1 with torch's align_corners=True semantics (source
+ * coordinate o*(in-1)/(out-1), A = -0.75, clamped taps, fp32 arithmetic), layout change fused:
+ * fp32 NCHW [N,C,H,W] -> NHWC dtype [N,H*s,W*s,Cp] (channels >= C zero). */
+int sr_bicubic_up(int dtype, const float* x, int N, int C, int H, int W, int s, int Cp, void* y, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Layout / elementwise ops (HBM-bound).
