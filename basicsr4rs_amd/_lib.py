@@ -18,6 +18,34 @@ LIB_PATH = switch('SR_HIP_LIB') or os.path.join(os.path.dirname(os.path.abspath(
 SR_F32, SR_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
 
+# sr_conv3x3_set_variant values: enum sr_conv_variant of include/sr_hip.h (there with what each reroutes)
+SR_VARIANT_AUTO = 0
+SR_VARIANT_TILE_ONLY = 1
+SR_VARIANT_TWO_BARRIER = 2
+SR_VARIANT_NO_PPH = 24
+SR_VARIANT_WG_NO_PARTIAL = 28
+SR_VARIANT_NO_TAIL = 29
+SR_VARIANT_REDUCE_PLAIN = 33
+SR_VARIANT_NO_BAND = 34
+SR_VARIANT_BAND_64 = 35
+SR_VARIANT_BAND_256 = 36
+SR_VARIANT_BAND_CS_ROWS = 37
+SR_VARIANT_PPH_NO_PS = 50
+SR_VARIANT_LIN_WIDE_BIG = 55
+SR_VARIANT_FOUR_PHASE = 59
+SR_VARIANT_PPH_P2_1 = 61
+SR_VARIANT_RING_WIDE_ALL = 62
+SR_VARIANT_NO_LINEAR_WGRAD = 63
+SR_VARIANT_NO_LINEAR_WK = 64
+SR_VARIANT_RING_NO_PS = 67
+SR_VARIANT_HALO_NO_PS = 68
+SR_VARIANT_NO_BAND_STRIP = 76
+SR_VARIANT_NO_PPH_STRIP = 77
+SR_VARIANT_NO_ROW3 = 78
+SR_VARIANT_NO_BIG_PARTIAL = 79
+SR_VARIANT_PPH_ONE_TILE = 80
+VARIANTS = {k: v for k, v in list(globals().items()) if k.startswith('SR_VARIANT_')}
+
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
 _f = ctypes.c_float

@@ -24,10 +24,19 @@
 
 namespace {
 
-// set by sr_conv3x3_set_variant (tests / A-B timing): 0 auto (phase-interleaved 256x256),
-// 1 never a 256x256 kernel, 2 the two-barrier 256x256 kernel (previous schedule)
-int g_variant = 0;
-#define g_disable_big (g_variant == 1)
+// set by sr_conv3x3_set_variant (tests / A-B timing): an sr_conv_variant of include/sr_hip.h
+int g_variant = SR_VARIANT_AUTO;
+bool variant_is(int v) { return g_variant == v; }
+// SR_VARIANT_TILE_ONLY: never a 256x256 kernel (nor any of the narrow-conv families)
+bool tile_only() { return variant_is(SR_VARIANT_TILE_ONLY); }
+
+// Bits of the compile-time epilogue code E of the band, lin and linear_wk kernels (a template argument, so
+// the values are part of the kernel names): bits 0-1 act, 2-3 gate (0 none, 1 pre-residual (g > 0 ? 1 :
+// gate_slope), 2 pre-residual GELU'(g), 3 post-residual mask on columns gcol0..gcol1), then one bit per operand.
+// Bit 7 is the channel sums in the band kernel and the per-image row scale in the lin kernels.
+enum : int { EPI_ACT = 3, EPI_GATE_SHIFT = 2, EPI_GATE = 3, EPI_RES = 16, EPI_RES2 = 32, EPI_AUX = 64 };
+enum : int { BAND_CS = 128, BAND_RSC = 256, BAND_DOT = 512, BAND_STRIP = 1024 };
+enum : int { LIN_RSC = 128 };
 
 struct FwdArgs {
   const void* x;
@@ -1527,9 +1536,10 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_pph_kernel(FwdArgs a) {
 template <int E>
 __global__ __launch_bounds__(256, 2) void linear_wk_kernel(FwdArgs a) {
   constexpr int XI = 128 * 128, WI = 192 * 128, STAGE = XI + WI;
-  constexpr int ACT = E & 3, GATE = (E >> 2) & 3;
-  constexpr bool RES = (E & 16) != 0, AUX = (E & 64) != 0, RSC = (E & 128) != 0;
-  static_assert(GATE != 3 && (E & ~(3 | 12 | 16 | 64 | 128)) == 0, "linear_wk: epilogue subset");
+  constexpr int ACT = E & EPI_ACT, GATE = (E >> EPI_GATE_SHIFT) & EPI_GATE;
+  constexpr bool RES = (E & EPI_RES) != 0, AUX = (E & EPI_AUX) != 0, RSC = (E & LIN_RSC) != 0;
+  static_assert(GATE != 3 && (E & ~(EPI_ACT | (EPI_GATE << EPI_GATE_SHIFT) | EPI_RES | EPI_AUX | LIN_RSC)) == 0,
+                "linear_wk: epilogue subset");
   __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1720,8 +1730,8 @@ template <int MT, int MAXCG, int NPASS, int E, bool LN = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_lin_kernel(FwdArgs a) {
   constexpr int NMT = MT / 16;  // token tiles per wave (every wave covers all MT tokens)
   constexpr bool CE = E >= 0;
-  constexpr int ACT = E & 3, GATE = (E >> 2) & 3;
-  constexpr bool RES = (E & 16) != 0, RES2 = (E & 32) != 0, AUX = (E & 64) != 0, RSC = (E & 128) != 0;
+  constexpr int ACT = E & EPI_ACT, GATE = (E >> EPI_GATE_SHIFT) & EPI_GATE;
+  constexpr bool RES = (E & EPI_RES) != 0, RES2 = (E & EPI_RES2) != 0, AUX = (E & EPI_AUX) != 0, RSC = (E & LIN_RSC) != 0;
   __shared__ __attribute__((aligned(16))) char smem[MAXCG * MT * 128];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2359,9 +2369,9 @@ constexpr int band_occ(int W, int E) {
 // 33.8 -> 37.0 ms, so 4 there.
 template <int CO, int W, int LA, int KH, int E, int NWV = 4>
 __global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : band_occ(W, E)) void conv3x3_fwd_band_kernel(FwdArgs a) {
-  constexpr int ACT = E & 3, GATE = (E >> 2) & 3;
-  constexpr bool RES = (E & 16) != 0, RES2 = (E & 32) != 0, AUX = (E & 64) != 0, CS = (E & 128) != 0,
-                 RSC = (E & 256) != 0, DOT = (E & 512) != 0, STRIP = (E & 1024) != 0;
+  constexpr int ACT = E & EPI_ACT, GATE = (E >> EPI_GATE_SHIFT) & EPI_GATE;
+  constexpr bool RES = (E & EPI_RES) != 0, RES2 = (E & EPI_RES2) != 0, AUX = (E & EPI_AUX) != 0, CS = (E & BAND_CS) != 0,
+                 RSC = (E & BAND_RSC) != 0, DOT = (E & BAND_DOT) != 0, STRIP = (E & BAND_STRIP) != 0;
   static_assert(!DOT || CS, "band: dot partials need colsum");
   static_assert(!STRIP || (!CS && !RSC), "band: column strips carry no per-image epilogue");
   constexpr int IR = GATE ? 1 : 0, IR2 = IR + (RES ? 1 : 0), ID = IR2 + (RES2 ? 1 : 0), NSTG = ID + (DOT ? 1 : 0);
@@ -4994,17 +5004,18 @@ hipError_t launch_fwd(const FwdArgs& a0, hipStream_t s) {
 }
 
 // pph over 64-px column strips (STRIP): bf16, W a multiple of 64 above 128 (EDSR at LR 256: the body
-// convs and their dgrads), H a multiple of 4, no pixel-shuffled input, no channel sums.  Variant 77:
-// the pp kernel for them (A/B, tests).
+// convs and their dgrads), H a multiple of 4, no pixel-shuffled input, no channel sums.
+// SR_VARIANT_NO_PPH_STRIP: the pp kernel for them (A/B, tests).
 bool fwd_use_pph_strip(const FwdArgs& a) {
-  return g_variant != 2 && g_variant != 24 && g_variant != 77 && a.W > 128 && a.W % 64 == 0 && a.H % 4 == 0 &&
-         a.Cin % 64 == 0 && a.in_ps == 0 && a.in_up == 1 && a.tap0 == 0 && !a.colsum;
+  return !variant_is(SR_VARIANT_TWO_BARRIER) && !variant_is(SR_VARIANT_NO_PPH) && !variant_is(SR_VARIANT_NO_PPH_STRIP) &&
+         a.W > 128 && a.W % 64 == 0 && a.H % 4 == 0 && a.Cin % 64 == 0 && a.in_ps == 0 && a.in_up == 1 && a.tap0 == 0 &&
+         !a.colsum;
 }
 // Halo variant of the 256x256 kernel: whole-row tiles of W = 64 / 128 images, 64-channel chunks.
 bool fwd_use_pph(const FwdArgs& a) {
-  return g_variant != 2 && g_variant != 24 &&
+  return !variant_is(SR_VARIANT_TWO_BARRIER) && !variant_is(SR_VARIANT_NO_PPH) &&
          ((a.W == 64 && a.H % 4 == 0) || (a.W == 128 && a.H % 2 == 0)) && a.Cin % 64 == 0 &&
-         (a.in_ps == 0 || (a.fd_cps.d % 64 == 0 && g_variant != 50)) && a.in_up == 1 && a.tap0 == 0;
+         (a.in_ps == 0 || (a.fd_cps.d % 64 == 0 && !variant_is(SR_VARIANT_PPH_NO_PS))) && a.in_up == 1 && a.tap0 == 0;
 }
 
 // Compute units of the current device, queried once per device (the persistent pph grid)
@@ -5024,13 +5035,34 @@ int device_cus() {
 // bias / activation / alpha and at most ONE of gate (modes 0, 1) and residual -- the EDSR / RCAN-style
 // body convs and their dgrads -- and more tiles than G blocks (with one tile per block the form is the
 // one-tile form).  G: the device's CU count, or knob SR_PPH_GRID (tests: several tiles per block at
-// small shapes).  Variant 80: the one-tile form for them (A/B, tests).
+// small shapes).  SR_VARIANT_PPH_ONE_TILE: the one-tile form for them (A/B, tests).
 int pph_pers_grid(const FwdArgs& a) {
-  if (g_variant == 80 || a.W != 64 || a.Cout != 256 || a.tiles_n != 1 || a.in_ps != 0 || a.out_ps != 0 || a.colsum || a.out_nchw ||
+  if (variant_is(SR_VARIANT_PPH_ONE_TILE) || a.W != 64 || a.Cout != 256 || a.tiles_n != 1 || a.in_ps != 0 || a.out_ps != 0 || a.colsum || a.out_nchw ||
       a.aux || a.res2 || a.row_scale || a.dot || (a.gate && a.res) || (a.gate && a.gate_mode == 2) || a.M % 256)
     return 0;
   const int G = sr_knob(K_PPH_GRID) > 0 ? sr_knob(K_PPH_GRID) : device_cus();
   return a.tiles > G ? G : 0;
+}
+
+// The pph form of a call fwd_use_pph takes: 2 rows per tile at W 128, 4 at W 64; the two-interval schedule with the B
+// prefetch (P2 2; W 64: persistent blocks where pph_pers_grid says so), without it (SR_VARIANT_PPH_P2_1) or the
+// 4-phase schedule (SR_VARIANT_FOUR_PHASE).
+void launch_pph(const FwdArgs& a, hipStream_t s) {
+  const dim3 grid(a.tiles), blk(512);
+  const bool w128 = a.W == 128;
+  if (variant_is(SR_VARIANT_FOUR_PHASE)) {
+    if (w128) hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<2, 0>), grid, blk, 0, s, a);
+    else hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<4, 0>), grid, blk, 0, s, a);
+  } else if (variant_is(SR_VARIANT_PPH_P2_1)) {
+    if (w128) hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<2, 1>), grid, blk, 0, s, a);
+    else hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<4, 1>), grid, blk, 0, s, a);
+  } else if (w128) {
+    hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<2, 2>), grid, blk, 0, s, a);
+  } else if (const int gp = pph_pers_grid(a)) {
+    hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<4, 2, false, true>), dim3(gp), blk, 0, s, a);
+  } else {
+    hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<4, 2>), grid, blk, 0, s, a);
+  }
 }
 
 hipError_t launch_fwd_big(const FwdArgs& a0, hipStream_t s) {
@@ -5039,27 +5071,18 @@ hipError_t launch_fwd_big(const FwdArgs& a0, hipStream_t s) {
   a.tiles_n = (a.Cout + 255) / 256;
   a.tiles = tm * a.tiles_n;
   a.stamps = g_sr_stamps;
-  if (g_variant == 2)
+  if (variant_is(SR_VARIANT_TWO_BARRIER)) {
     hipLaunchKernelGGL(conv3x3_fwd_big_kernel, dim3(a.tiles), dim3(512), 0, s, a);
-  else if (fwd_use_pph_strip(a)) {
+  } else if (fwd_use_pph_strip(a)) {
     a.strip64 = 1;
     hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<4, 2, true>), dim3(a.tiles), dim3(512), 0, s, a);
-  } else if (fwd_use_pph(a) && a.W == 128 && g_variant != 59)
-    if (g_variant == 61) hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<2, 1>), dim3(a.tiles), dim3(512), 0, s, a);
-    else hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<2, 2>), dim3(a.tiles), dim3(512), 0, s, a);
-  else if (fwd_use_pph(a) && a.W == 128)
-    hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<2, 0>), dim3(a.tiles), dim3(512), 0, s, a);
-  else if (g_variant != 59 && fwd_use_pph(a))
-    if (g_variant == 61) hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<4, 1>), dim3(a.tiles), dim3(512), 0, s, a);
-    else if (const int gp = pph_pers_grid(a))
-      hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<4, 2, false, true>), dim3(gp), dim3(512), 0, s, a);
-    else hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<4, 2>), dim3(a.tiles), dim3(512), 0, s, a);
-  else if (fwd_use_pph(a))
-    hipLaunchKernelGGL((conv3x3_fwd_pph_kernel<4, 0>), dim3(a.tiles), dim3(512), 0, s, a);
-  else if ((a.Cin % 64 == 0 || a.tap0 == 4) && (a.in_ps == 0 || a.fd_cps.d % 64 == 0))
+  } else if (fwd_use_pph(a)) {
+    launch_pph(a, s);
+  } else if ((a.Cin % 64 == 0 || a.tap0 == 4) && (a.in_ps == 0 || a.fd_cps.d % 64 == 0)) {
     hipLaunchKernelGGL(conv3x3_fwd_pp_kernel<true>, dim3(a.tiles), dim3(512), 0, s, a);
-  else
+  } else {
     hipLaunchKernelGGL(conv3x3_fwd_pp_kernel<false>, dim3(a.tiles), dim3(512), 0, s, a);
+  }
   return hipGetLastError();
 }
 
@@ -5069,11 +5092,11 @@ hipError_t launch_fwd_big(const FwdArgs& a0, hipStream_t s) {
 // in round 5: EDSR conv_last dgrad 1390 vs 550 us, profiles/r04/halo256/.)
 bool fwd_use_halo(const FwdArgs& a, bool bf) {
   // pixel-shuffled input (the upsample convs' dgrads into 64 channels) when each 64-channel chunk lies
-  // in one shuffle slot; variant 68: the tile kernel for those (A/B)
-  const bool ps_ok = a.in_ps > 0 && a.fd_cps.d % 64 == 0 && a.W != 256 && g_variant != 68;
-  if (!bf || a.in_up != 1 || (a.in_ps != 0 && !ps_ok) || a.tap0 != 0 || g_variant == 1) return false;
+  // in one shuffle slot; SR_VARIANT_HALO_NO_PS: the tile kernel for those (A/B)
+  const bool ps_ok = a.in_ps > 0 && a.fd_cps.d % 64 == 0 && a.W != 256 && !variant_is(SR_VARIANT_HALO_NO_PS);
+  if (!bf || a.in_up != 1 || (a.in_ps != 0 && !ps_ok) || a.tap0 != 0 || tile_only()) return false;
   if (a.W == 256)  // HR-resolution tail convs (conv_last, Cout <= 16, NCHW store): one row per tile
-    return a.Cout <= 16 && g_variant != 29;
+    return a.Cout <= 16 && !variant_is(SR_VARIANT_NO_TAIL);
   return !a.out_nchw && a.Cout < 256 && (a.W == 64 || a.W == 128) && a.H % (256 / a.W) == 0;
 }
 
@@ -5097,15 +5120,17 @@ hipError_t launch_fwd_halo(const FwdArgs& a0, hipStream_t s) {
 // Kernel family sr_conv3x3_fwd launches for a call (dispatch, kernel names and the
 // epilogue geometry behind colsum all follow this one choice).
 enum FwdKind { FK_HALO, FK_BIG, FK_256_16, FK_256_32, FK_128_64, FK_128_128, FK_LIN, FK_BAND, FK_TAIL, FK_BANDS };
-// row-streaming narrow conv: bf16 3x3, Cin 32 / 64, Cout 32 / 64 exactly, W 64 / 128, plain or
-// channel-slice NHWC in and out (variant 34: the tile kernel instead, for A/B)
+// the bits of a compile-time epilogue code that the band and lin kernels share (EPI_*)
+int epi_common(const FwdArgs& a) {
+  int gate = 0;
+  if (a.gate) gate = a.gate_mode == 2 ? 3 : (a.gate_mode == 1 ? 2 : 1);
+  return a.act | (gate << EPI_GATE_SHIFT) | (a.res ? EPI_RES : 0) | (a.res2 ? EPI_RES2 : 0) | (a.aux ? EPI_AUX : 0);
+}
 // the band kernel's compile-time epilogue code (see conv3x3_fwd_band_kernel) for these arguments,
 // -1 when it is not one of the instantiated ones
 int band_epi(const FwdArgs& a, int grid) {
-  int gate = 0;
-  if (a.gate) gate = a.gate_mode == 2 ? 3 : (a.gate_mode == 1 ? 2 : 1);
-  const int e = a.act | (gate << 2) | (a.res ? 16 : 0) | (a.res2 ? 32 : 0) | (a.aux ? 64 : 0) |
-                (a.colsum || a.dot ? 128 : 0) | (a.row_scale ? 256 : 0) | (a.dot ? 512 : 0);  // dot implies colsum
+  const int e = epi_common(a) | (a.colsum || a.dot ? BAND_CS : 0) | (a.row_scale ? BAND_RSC : 0) |
+                (a.dot ? BAND_DOT : 0);  // dot implies colsum
   if (a.row_scale) {  // the images of one band fit one wave's lanes
     const int rows = (a.N * a.H + grid - 1) / grid;
     if ((rows + a.H - 1) / a.H + 1 > 64) return -1;
@@ -5116,25 +5141,35 @@ int band_epi(const FwdArgs& a, int grid) {
     default: return -1;
   }
 }
+// Blocks of a band launch over `rows` image rows (or strip rows): one block per CU (one wave per SIMD: the weights
+// live in registers); SR_VARIANT_BAND_64 forces 64 blocks (long bands: ring wrap-around and image / strip crossings
+// inside a band, for tests).  (Two bands per CU for the band_occ forms measured faster alone but slower in the RCAN
+// step beside the side-stream weight gradients; the switch was removed in round 5.)
+int band_grid(int rows) {
+  const int gmax = variant_is(SR_VARIANT_BAND_64) ? 64 : 256;
+  return rows < gmax ? rows : gmax;
+}
+bool band_off() { return tile_only() || variant_is(SR_VARIANT_NO_BAND); }  // the tile kernel instead (A/B, tests)
+// row-streaming narrow conv: bf16 3x3, Cin 32 / 64, Cout 32 / 64 exactly, W 64 / 128, plain or
+// channel-slice NHWC in and out
 bool fwd_use_band(const FwdArgs& a, bool bf) {
   if (!(bf && a.tap0 == 0 && a.in_up == 1 && a.in_ps == 0 && !a.out_nchw && a.out_ps == 0 &&
         (a.W == 64 || a.W == 128) && (a.Cin == 32 || a.Cin == 64) && (a.Cout == 32 || a.Cout == 64) &&
-        a.Cout_real == a.Cout && g_variant != 1 && g_variant != 34))  // 34: the tile kernel (A/B, tests)
+        a.Cout_real == a.Cout && !band_off()))
     return false;
-  const int rows = a.N * a.H, gmax = g_variant == 35 ? 64 : 256;
-  return band_epi(a, rows < gmax ? rows : gmax) >= 0;
+  return band_epi(a, band_grid(a.N * a.H)) >= 0;
 }
 // 64-channel-output convs on images wider than 128 px (W 256 / 512: the RRDBNet HR convs conv_up1 /
 // conv_up2 / conv_hr, their dgrads and conv_last's dgrad from its 8 padded output channels), and W 128
 // with the nearest x2 upsample folded in, as band launches over 128-px column strips (STRIP: E bit
 // 10): Cin 64 with a plain, ReLU, LeakyReLU or lrelu-gate epilogue, Cin 8..32 plain or gated.
-// Variant 76: the generic tile kernel for them (A/B, tests).
+// SR_VARIANT_NO_BAND_STRIP: the generic tile kernel for them (A/B, tests).
 bool fwd_use_band_strip(const FwdArgs& a, bool bf) {
   if (!(bf && a.tap0 == 0 && (a.in_up == 1 || a.in_up == 2) && a.in_ps == 0 && !a.out_nchw && a.out_ps == 0 &&
         a.W % 128 == 0 && (a.W > 128 || a.in_up == 2) && (a.Cin == 64 || (a.Cin <= 32 && a.Cin % 8 == 0)) &&
         (a.Cout == 64 || (a.Cin <= 32 && (a.Cout == 128 || a.Cout == 256))) && a.Cout_real == a.Cout &&
-        !a.colsum && !a.dot && !a.row_scale && !a.res2 && !a.aux && g_variant != 1 && g_variant != 34 &&
-        g_variant != 76))
+        !a.colsum && !a.dot && !a.row_scale && !a.res2 && !a.aux && !band_off() &&
+        !variant_is(SR_VARIANT_NO_BAND_STRIP)))
     return false;
   const int e = band_epi(a, 256);
   if (a.Cout > 64) return e == 0;  // 8-channel input into 128 / 256 (EDSR's conv_last dgrad): one launch
@@ -5155,20 +5190,16 @@ bool fwd_use_band_strip_sliced(const FwdArgs& a, bool bf) {
 bool fwd_use_band_sliced(const FwdArgs& a, bool bf) {
   if (!(bf && a.tap0 == 0 && a.in_up == 1 && a.in_ps == 0 && !a.out_nchw && a.out_ps == 0 &&
         (a.W == 64 || a.W == 128) && (a.Cin == 32 || a.Cin == 64) && a.Cout > 64 && a.Cout < 256 &&
-        a.Cout % 32 == 0 && a.Cout_real == a.Cout && !a.colsum && g_variant != 1 && g_variant != 34))
+        a.Cout % 32 == 0 && a.Cout_real == a.Cout && !a.colsum && !band_off()))
     return false;
-  const int rows = a.N * a.H, gmax = g_variant == 35 ? 64 : 256;
-  return band_epi(a, rows < gmax ? rows : gmax) >= 0;
+  return band_epi(a, band_grid(a.N * a.H)) >= 0;
 }
 // the lin kernel's compile-time epilogue code for these arguments (see conv3x3_lin_kernel), -1
 // for the run-time-flag form; instantiated: plain (qkv fwd, proj dgrad), GELU' gate (fc2
 // dgrad), residual (proj fwd), GELU + pre-activation (fc1 fwd), residual + row scale (proj
 // fwd with stochastic depth)
 int lin_epi(const FwdArgs& a) {
-  int gate = 0;
-  if (a.gate) gate = a.gate_mode == 2 ? 3 : (a.gate_mode == 1 ? 2 : 1);
-  const int e = a.act | (gate << 2) | (a.res ? 16 : 0) | (a.res2 ? 32 : 0) | (a.aux ? 64 : 0) |
-                (a.row_scale ? 128 : 0);
+  const int e = epi_common(a) | (a.row_scale ? LIN_RSC : 0);
   if (a.row_scale && (a.H * a.W) % 128) return -1;  // row scale uniform per 128-token block
   if ((size_t)a.M * a.ldy * 2 >= 0x80000000ull) return -1;  // buffer-store offsets are 31-bit
   switch (e) {
@@ -5178,19 +5209,20 @@ int lin_epi(const FwdArgs& a) {
 }
 // short-K 1x1 convs (linears): token tile staged once, all output channels swept.  K <= 192 on
 // 128-token tiles; 192 < K <= 576 (SwinIR fc2 fwd 360 -> 184, fc1 / qkv dgrads 360 / 576 -> 184) on
-// 64-token tiles, Cout <= 384 (variant 55: those on the 256x256 pp kernel instead, for A/B)
+// 64-token tiles, Cout <= 384 (SR_VARIANT_LIN_WIDE_BIG: those on the 256x256 pp kernel instead, for A/B)
 bool fwd_use_lin(const FwdArgs& a, bool bf) {
-  if (!(bf && a.tap0 == 4 && !a.out_nchw && a.out_ps == 0 && a.in_ps == 0 && a.in_up == 1 && g_variant != 1))
+  if (!(bf && a.tap0 == 4 && !a.out_nchw && a.out_ps == 0 && a.in_ps == 0 && a.in_up == 1 && !tile_only()))
     return false;
   if (a.Cin <= 192) return a.Cout <= 640;
-  return a.Cin <= 576 && a.Cout <= 384 && g_variant != 55;
+  return a.Cin <= 576 && a.Cout <= 384 && !variant_is(SR_VARIANT_LIN_WIDE_BIG);
 }
 // linear_wk_kernel for the linears with K > SR_LWK_MINK (default 0: all; 192: only the wide-K ones,
 // which the 64-token lin kernel took), K <= 576, 96 < Cout <= 576 and a plain / GELU' gate / GELU +
-// pre-activation / residual / residual + row-scale epilogue; knob SR_LWK=0 or variant 64: the lin kernel (A/B, tests)
+// pre-activation / residual / residual + row-scale epilogue; knob SR_LWK=0 or SR_VARIANT_NO_LINEAR_WK: the lin
+// kernel (A/B, tests)
 bool lin_use_wk(const FwdArgs& a) {
   const int mink = sr_knob(K_LWK) == 0 ? (1 << 30) : (sr_knob(K_LWK_MINK) > 0 ? sr_knob(K_LWK_MINK) : 0);
-  if (g_variant == 64 || a.Cin <= mink || a.Cin > 576 || a.Cout > 576 || a.Cout <= 96) return false;
+  if (variant_is(SR_VARIANT_NO_LINEAR_WK) || a.Cin <= mink || a.Cin > 576 || a.Cout > 576 || a.Cout <= 96) return false;
   const int e = lin_epi(a);
   return e == 0 || e == 8 || e == 16 || e == 67 || e == 144;
 }
@@ -5198,7 +5230,7 @@ bool lin_use_wk(const FwdArgs& a) {
 bool fwd_use_tail(const FwdArgs& a, bool bf) {
   return bf && a.tap0 == 0 && a.in_up == 1 && a.in_ps == 0 && a.out_ps == 0 && a.out_nchw && a.Cout <= 16 &&
          a.W >= 256 && a.W % 32 == 0 && (a.Cin == 64 || a.Cin == 128 || a.Cin == 256) && !a.gate && !a.res && !a.res2 &&
-         !a.aux && !a.colsum && !a.row_scale && g_variant != 1 && g_variant != 29;
+         !a.aux && !a.colsum && !a.row_scale && !tile_only() && !variant_is(SR_VARIANT_NO_TAIL);
 }
 FwdKind fwd_kind(const FwdArgs& a, bool bf) {
   if (fwd_use_tail(a, bf)) return FK_TAIL;
@@ -5207,15 +5239,15 @@ FwdKind fwd_kind(const FwdArgs& a, bool bf) {
   if (fwd_use_band_sliced(a, bf) || fwd_use_band_strip_sliced(a, bf)) return FK_BANDS;
   // 128 < Cout < 256 from Cin >= 128, K a multiple of 64 (SwinIR-M's 180 -> 180 convs with the GEMM K padded
   // to 192 on the host, ops/conv.py _kpad): the halo-row 256x256 kernel with a partial output tile rather
-  // than the 64-channel halo kernel (variant 79: the halo kernel, A/B and tests)
+  // than the 64-channel halo kernel (SR_VARIANT_NO_BIG_PARTIAL: the halo kernel, A/B and tests)
   if (bf && a.Cout > 128 && a.Cout < 256 && a.Cin >= 128 && !a.out_nchw && a.out_ps == 0 && !a.colsum &&
-      !a.dot && fwd_use_pph(a) && !g_disable_big && g_variant != 79)
+      !a.dot && fwd_use_pph(a) && !tile_only() && !variant_is(SR_VARIANT_NO_BIG_PARTIAL))
     return FK_BIG;
   if (fwd_use_halo(a, bf)) return FK_HALO;
   // 1x1 convs with K > 192 (SwinIR fc2 fwd, qkv / fc1 dgrads: K 368 / 576 -> 184) on the 256x256
   // kernel with a partial N tile: x read once (vs twice by 128x128 tiles); 68 -> 57 us and 82 -> 65 us
   const bool lin_big = a.tap0 == 4 && a.Cin > 192 && a.Cout >= 128;
-  if (bf && !a.out_nchw && (a.Cout >= 256 || lin_big) && a.in_up == 1 && !g_disable_big) return FK_BIG;
+  if (bf && !a.out_nchw && (a.Cout >= 256 || lin_big) && a.in_up == 1 && !tile_only()) return FK_BIG;
   if (a.out_nchw || a.Cout <= 16) return FK_256_16;
   if (a.Cout <= 32) return FK_256_32;
   if (a.Cout <= 64) return FK_128_64;
@@ -5235,29 +5267,30 @@ void fwd_epi_geom(FwdKind k, int* rows, int* nt) {
 // image (rows per band divides H), each band leaves one partial row per pixel wave instead of one per
 // row -- RCAN B 32: 16 instead of 128 partial rows per image, the count the standalone partials pass
 // (sr_channel_partials) gives, so the channel-attention kernels that sum them stage 8x less.  Returns
-// the rows per band, 0 when the sums stay per row.  Variant 37: per-row sums (tests).
-int band_grid(const FwdArgs& a) {
-  const int rows = a.N * a.H, gmax = g_variant == 35 ? 64 : 256;
-  return rows < gmax ? rows : gmax;
-}
+// the rows per band, 0 when the sums stay per row.  SR_VARIANT_BAND_CS_ROWS: per-row sums (tests).
 int band_cs_rows(const FwdArgs& a) {
-  const int T = a.N * a.H, G = band_grid(a);
-  if (g_variant == 37 || T % G || a.H % (T / G) || T / G < 2) return 0;
+  const int T = a.N * a.H, G = band_grid(T);
+  if (variant_is(SR_VARIANT_BAND_CS_ROWS) || T % G || a.H % (T / G) || T / G < 2) return 0;
   return T / G;
 }
 int band_nwv(const FwdArgs& a) {
   return a.W == 128 && !(a.Cout == 32 && (a.colsum || a.dot)) ? 8 : 4;
 }
-hipError_t launch_band8(const FwdArgs& a, hipStream_t s) {
-  const int rows = a.N * a.H;
+// the whole-row forms on NWV waves per block (band_nwv)
+template <int NWV>
+hipError_t launch_band_rows(const FwdArgs& a, hipStream_t s) {
   FwdArgs ab = a;
   ab.stamps = g_sr_stamps;
   ab.cs_band = a.colsum ? band_cs_rows(a) : 0;
-  const int gmax = g_variant == 35 ? 64 : 256;
-  const dim3 grid(rows < gmax ? rows : gmax);
+  const dim3 grid(band_grid(a.N * a.H)), blk(NWV * 64);
   const int e = band_epi(a, grid.x);
+  if (e == 656) {  // instantiated for the RCAN shapes only
+    if (a.W == 64) hipLaunchKernelGGL((conv3x3_fwd_band_kernel<64, 64, 5, 2, 656>), grid, dim3(256), 0, s, ab);
+    else hipLaunchKernelGGL((conv3x3_fwd_band_kernel<64, 128, 3, 2, 656, NWV>), grid, blk, 0, s, ab);
+    return hipGetLastError();
+  }
 #define SR_BAND_E(CO_, W_, LA_, KH_, E_) \
-  case E_: hipLaunchKernelGGL((conv3x3_fwd_band_kernel<CO_, W_, LA_, KH_, E_, 8>), grid, dim3(512), 0, s, ab); break;
+  case E_: hipLaunchKernelGGL((conv3x3_fwd_band_kernel<CO_, W_, LA_, KH_, E_, NWV>), grid, blk, 0, s, ab); break;
 #define SR_BAND(CO_, W_, LA_, KH_) \
   if (a.Cout == CO_ && a.W == W_ && a.Cin == 32 * KH_) { \
 switch (e) { \
@@ -5270,9 +5303,8 @@ switch (e) { \
 } \
 return hipGetLastError(); \
   }
-  if (e == 656) {  // instantiated for the RCAN shapes only
-    hipLaunchKernelGGL((conv3x3_fwd_band_kernel<64, 128, 3, 2, 656, 8>), grid, dim3(512), 0, s, ab);
-    return hipGetLastError();
+  if constexpr (NWV == 4) {  // W 64: one pixel tile per wave
+    SR_BAND(64, 64, 5, 2) SR_BAND(64, 64, 5, 1) SR_BAND(32, 64, 5, 2) SR_BAND(32, 64, 5, 1)
   }
   SR_BAND(64, 128, 3, 2) SR_BAND(64, 128, 3, 1) SR_BAND(32, 128, 4, 2) SR_BAND(32, 128, 4, 1)
 #undef SR_BAND
@@ -5283,8 +5315,7 @@ hipError_t launch_band_strip(const FwdArgs& a, hipStream_t s) {
   const int rows = a.N * a.H * (a.W / 128);
   FwdArgs ab = a;
   ab.stamps = g_sr_stamps;
-  const int gmax = g_variant == 35 ? 64 : 256;  // 35: long bands crossing strips and images (tests)
-  const dim3 grid(rows < gmax ? rows : gmax);
+  const dim3 grid(band_grid(rows));
   if (a.Cin <= 32 && a.Cout > 64) {  // plain epilogue only (fwd_use_band_strip)
     if (a.Cout == 256) hipLaunchKernelGGL((conv3x3_fwd_band_kernel<256, 128, 3, 1, 1024, 8>), grid, dim3(512), 0, s, ab);
     else hipLaunchKernelGGL((conv3x3_fwd_band_kernel<128, 128, 3, 1, 1024, 8>), grid, dim3(512), 0, s, ab);
@@ -5309,42 +5340,7 @@ hipError_t launch_band_strip(const FwdArgs& a, hipStream_t s) {
 }
 hipError_t launch_band(const FwdArgs& a, hipStream_t s) {
   if (a.W > 128 || a.in_up != 1) return launch_band_strip(a, s);
-  if (band_nwv(a) == 8) return launch_band8(a, s);
-  // one block per CU (one wave per SIMD: the weights live in registers); variant 35 forces 64 blocks
-  // (long bands: ring wrap-around and image crossings inside a band, for tests).  (Two bands per CU
-  // for the band_occ forms measured faster alone but slower in the RCAN step beside the side-stream
-  // weight gradients; the switch was removed in round 5.)
-  const int rows = a.N * a.H;
-  const int gmax = g_variant == 35 ? 64 : 256;
-  FwdArgs ab = a;
-  ab.stamps = g_sr_stamps;
-  ab.cs_band = a.colsum ? band_cs_rows(a) : 0;
-  const dim3 grid(rows < gmax ? rows : gmax);
-  const int e = band_epi(a, grid.x);
-  if (e == 656) {  // instantiated for the RCAN shapes only
-    if (a.W == 64) hipLaunchKernelGGL((conv3x3_fwd_band_kernel<64, 64, 5, 2, 656>), grid, dim3(256), 0, s, ab);
-    else hipLaunchKernelGGL((conv3x3_fwd_band_kernel<64, 128, 3, 2, 656>), grid, dim3(256), 0, s, ab);
-    return hipGetLastError();
-  }
-#define SR_BAND_E(CO_, W_, LA_, KH_, E_) \
-  case E_: hipLaunchKernelGGL((conv3x3_fwd_band_kernel<CO_, W_, LA_, KH_, E_>), grid, dim3(256), 0, s, ab); break;
-#define SR_BAND(CO_, W_, LA_, KH_) \
-  if (a.Cout == CO_ && a.W == W_ && a.Cin == 32 * KH_) { \
-switch (e) { \
-  SR_BAND_E(CO_, W_, LA_, KH_, 0) SR_BAND_E(CO_, W_, LA_, KH_, 1) SR_BAND_E(CO_, W_, LA_, KH_, 2) \
-  SR_BAND_E(CO_, W_, LA_, KH_, 4) SR_BAND_E(CO_, W_, LA_, KH_, 16) SR_BAND_E(CO_, W_, LA_, KH_, 20) \
-  SR_BAND_E(CO_, W_, LA_, KH_, 28) \
-  SR_BAND_E(CO_, W_, LA_, KH_, 48) SR_BAND_E(CO_, W_, LA_, KH_, 72) SR_BAND_E(CO_, W_, LA_, KH_, 128) \
-  SR_BAND_E(CO_, W_, LA_, KH_, 304) \
-  default: return hipErrorInvalidValue; \
-} \
-return hipGetLastError(); \
-  }
-  SR_BAND(64, 64, 5, 2) SR_BAND(64, 64, 5, 1) SR_BAND(32, 64, 5, 2) SR_BAND(32, 64, 5, 1)
-  SR_BAND(64, 128, 3, 2) SR_BAND(64, 128, 3, 1) SR_BAND(32, 128, 4, 2) SR_BAND(32, 128, 4, 1)
-#undef SR_BAND
-#undef SR_BAND_E
-  return hipErrorInvalidValue;
+  return band_nwv(a) == 8 ? launch_band_rows<8>(a, s) : launch_band_rows<4>(a, s);
 }
 
 template <typename T>
@@ -5492,18 +5488,19 @@ hipError_t dispatch_wg(const WgArgs& a, hipStream_t s) {
 // columns of the tile) -- far fewer operand re-reads than 128x128 tiles.
 bool wg_use_pp_partial(const sr_conv3x3_wgrad_desc* d) {
   return d->dtype == SR_BF16 && d->Cout >= 128 && d->Cin >= 128 && d->W % 64 == 0 &&
-         d->in_up <= 1 && d->out_ps == 0 && !g_disable_big && g_variant != 2 && g_variant != 28;
+         d->in_up <= 1 && d->out_ps == 0 && !tile_only() && !variant_is(SR_VARIANT_TWO_BARRIER) &&
+         !variant_is(SR_VARIANT_WG_NO_PARTIAL);
 }
 
 bool wg_use_big(const sr_conv3x3_wgrad_desc* d) {
-  return (d->dtype == SR_BF16 && d->Cout >= 256 && d->Cin >= 256 && d->in_up <= 1 && !g_disable_big) ||
+  return (d->dtype == SR_BF16 && d->Cout >= 256 && d->Cin >= 256 && d->in_up <= 1 && !tile_only()) ||
          wg_use_pp_partial(d);
 }
 
 // Phase-interleaved wgrad kernel: W a multiple of 64, channel counts (and the pixel-shuffle
 // slot width) multiples of 128.
 bool wg_use_pp(const sr_conv3x3_wgrad_desc* d) {
-  if (!wg_use_big(d) || g_variant == 2) return false;
+  if (!wg_use_big(d) || variant_is(SR_VARIANT_TWO_BARRIER)) return false;
   if (wg_use_pp_partial(d)) return true;
   const int cps = d->out_ps > 0 ? d->Cout / (d->out_ps * d->out_ps) : 128;
   return d->W % 64 == 0 && d->Cout % 128 == 0 && d->Cin % 128 == 0 && cps % 128 == 0;
@@ -5536,46 +5533,47 @@ bool wg_bias_fused(const sr_conv3x3_wgrad_desc* d) {
 // (the head convs); on the EDSR-L body shape it ties the pp kernel (193 vs 189 us; 256 blocks 256 us,
 // 3 / 4 steps in flight 250-280 us: LDS for one block per CU), which stays there.
 // knob SR_RING_WIDE: 0 = off, > 0 = on for every Cout > 64 shape with that block target (A/B);
-// variant 62: on everywhere (parity tests).
+// SR_VARIANT_RING_WIDE_ALL: on everywhere (parity tests).
 int ring_wide_env() {
   const int x = sr_knob(K_RING_WIDE);
   return x >= -1 && x <= 4096 ? x : -1;
 }
 int ring_wide_target() {
-  if (g_variant == 62) return 512;
+  if (variant_is(SR_VARIANT_RING_WIDE_ALL)) return 512;
   const int v = ring_wide_env();
   return v < 0 ? 512 : v;
 }
 bool wg_ring_wide(const sr_conv3x3_wgrad_desc* d) {
-  if (ring_wide_target() <= 0 || g_variant == 1 || d->dtype != SR_BF16 || d->ksize == 1 || d->Cout <= 64 ||
+  if (ring_wide_target() <= 0 || tile_only() || d->dtype != SR_BF16 || d->ksize == 1 || d->Cout <= 64 ||
       d->W % 64 || d->in_up > 2)
     return false;
-  const bool ps_off = sr_knob(K_RING_PS) == 0;
-  if (d->out_ps > 0 && (d->in_up > 1 || (d->Cout / (d->out_ps * d->out_ps)) % 64 != 0 || g_variant == 67 || ps_off))
-    return false;  // pixel-shuffled dy: each 64-wide co tile inside one shuffle slot; variant 67 / knob SR_RING_PS=0: off (A/B)
-  if (g_variant == 62 || ring_wide_env() > 0) return true;
+  // pixel-shuffled dy: each 64-wide co tile inside one shuffle slot; SR_VARIANT_RING_NO_PS / knob SR_RING_PS=0: off (A/B)
+  const bool ps_off = sr_knob(K_RING_PS) == 0 || variant_is(SR_VARIANT_RING_NO_PS);
+  if (d->out_ps > 0 && (d->in_up > 1 || (d->Cout / (d->out_ps * d->out_ps)) % 64 != 0 || ps_off)) return false;
+  if (variant_is(SR_VARIANT_RING_WIDE_ALL) || ring_wide_env() > 0) return true;
   return d->Cout % 128 != 0 || d->Cin % 128 != 0;
 }
 // Kernel-row wgrad (conv3x3_wgrad_row3_kernel): bf16 3x3, Cout % 256, Cin % 128, W % 64, no upsample,
-// pixel-shuffled dy when a 256-co tile lies in one shuffle slot (the EDSR-L body and upsample convs).  Knob SR_WG_ROW3=0 or variant 78: the pp kernel (A/B, parity
-// cross-check); SR_WG_ROW3=k > 0: bias-role blocks of k splits (default 2).
+// pixel-shuffled dy when a 256-co tile lies in one shuffle slot (the EDSR-L body and upsample convs).  Knob
+// SR_WG_ROW3=0 or SR_VARIANT_NO_ROW3: the pp kernel (A/B, parity cross-check); SR_WG_ROW3=k > 0: bias-role
+// blocks of k splits (default 2).
 int wg_row3_bg() {
   const int k = sr_knob(K_WG_ROW3);
   return k > 0 && k <= 64 ? k : 2;
 }
 bool wg_use_row3(const sr_conv3x3_wgrad_desc* d) {
-  if (sr_knob(K_WG_ROW3) == 0 || g_variant == 1 || g_variant == 2 || g_variant == 28 || g_variant == 62 ||
-      g_variant == 78)
+  if (sr_knob(K_WG_ROW3) == 0 || tile_only() || variant_is(SR_VARIANT_TWO_BARRIER) ||
+      variant_is(SR_VARIANT_WG_NO_PARTIAL) || variant_is(SR_VARIANT_RING_WIDE_ALL) || variant_is(SR_VARIANT_NO_ROW3))
     return false;
   const bool ps_ok = d->out_ps == 0 || (d->Cout / (d->out_ps * d->out_ps)) % 256 == 0;  // a co tile in one slot
   return d->dtype == SR_BF16 && d->ksize != 1 && d->Cout % 256 == 0 && d->Cin % 128 == 0 && d->W % 64 == 0 &&
          ps_ok && d->in_up <= 1 && ring_wide_env() <= 0;
 }
 // 1x1 weight gradient on linear_wgrad_kernel (192x192 tiles): bf16 dense token rows, no pixel
-// shuffle / upsample.  Knob SR_LWG=0 or variant 63: off (the pp kernel, A/B and tests).
+// shuffle / upsample.  Knob SR_LWG=0 or SR_VARIANT_NO_LINEAR_WGRAD: off (the pp kernel, A/B and tests).
 bool wg_use_lin(const sr_conv3x3_wgrad_desc* d) {
-  const bool off = sr_knob(K_LWG) == 0;
-  return !off && g_variant != 63 && g_variant != 1 && d->dtype == SR_BF16 && d->ksize == 1 && d->in_up <= 1 &&
+  const bool off = sr_knob(K_LWG) == 0 || variant_is(SR_VARIANT_NO_LINEAR_WGRAD);
+  return !off && !tile_only() && d->dtype == SR_BF16 && d->ksize == 1 && d->in_up <= 1 &&
          d->out_ps == 0 && d->Cout >= 64 && d->Cin >= 64;
 }
 // Block target of its split plan: 128 (half the chip: it runs on the weight-gradient side stream beside
@@ -5590,7 +5588,7 @@ int lin_wg_target() {
 bool wg_use_halo(const sr_conv3x3_wgrad_desc* d) {
   if (wg_ring_wide(d)) return true;
   return d->dtype == SR_BF16 && d->ksize != 1 && d->Cout <= 64 && d->W % 64 == 0 && d->in_up <= 2 && d->out_ps == 0 &&
-         g_variant != 1;
+         !tile_only();
 }
 
 // Block target of the narrow ring wgrad split plan: 512, or knob SR_RING_SPLITS (A/B sweeps)
@@ -5604,10 +5602,22 @@ int ring_tiles_co(const sr_conv3x3_wgrad_desc* d) { return wg_ring_wide(d) ? (d-
 
 // Split-K factor: enough blocks to cover the chip (~1 round of 256 one-per-CU blocks for the
 // 256x256 kernel, ~2 rounds for the small ones), pixels per split a multiple of 64.
+// S clamped to [1, maxS], pixels per split = ceil(M / S) rounded up to 64, splits = the ranges that leaves
+void plan_splits(int M, int S, int maxS, int* splits, int* kper) {
+  if (S > maxS) S = maxS;
+  if (S < 1) S = 1;
+  const int kp = ((M + S - 1) / S + 63) / 64 * 64;
+  *splits = (M + kp - 1) / kp;
+  *kper = kp;
+}
+// Most splits S of one 256-block wave: S x ntile tile blocks + ceil(S / bg) x tco bias-role blocks
+int one_wave_splits(int ntile, int tco, int bg) {
+  int S = (int)(256.0 / (ntile + (double)tco / bg));
+  while (S > 1 && S * ntile + (S + bg - 1) / bg * tco > 256) --S;
+  return S;
+}
 void wgrad_plan(const sr_conv3x3_wgrad_desc* d, int* splits, int* kper) {
   const int M = d->N * d->H * d->W;
-  int bm, bn, target;
-  int extra = 0;  // bias-role blocks per split (big kernel)
   if (wg_use_halo(d)) {
     // ~2 blocks per CU, but at least 8 K-steps per block (the slab costs 8 B per tap-MAC row)
     // (A/B on RCAN / RRDB: twice or half as many splits are 6-12 % slower per step)
@@ -5623,77 +5633,28 @@ void wgrad_plan(const sr_conv3x3_wgrad_desc* d, int* splits, int* kper) {
     *kper = rps * d->W;
     return;
   }
+  const int tco = (d->Cout + 255) / 256, tci = (d->Cin + 255) / 256;  // 256x256 tiles
   if (wg_use_lin(d)) {
     const int tiles = ((d->Cout + 191) / 192) * ((d->Cin + 191) / 192);
-    int S = lin_wg_target() / tiles;
-    const int maxS = (M + 63) / 64;
-    if (S > maxS) S = maxS;
-    if (S < 1) S = 1;
-    int kp = (M + S - 1) / S;
-    kp = (kp + 63) / 64 * 64;
-    *splits = (M + kp - 1) / kp;
-    *kper = kp;
-    return;
+    return plan_splits(M, lin_wg_target() / tiles, (M + 63) / 64, splits, kper);
   }
-  if (wg_use_row3(d)) {  // one 256-block wave: S x 3 x tiles tile blocks + the bias-role blocks
-    const int bg = wg_row3_bg(), tco = d->Cout / 256;
-    const int ntile = 3 * tco * (d->Cin / 128);
-    int S = (int)(256.0 / (ntile + (double)tco / bg));
-    while (S > 1 && S * ntile + (S + bg - 1) / bg * tco > 256) --S;
-    const int maxS = M / 64;
-    if (S > maxS) S = maxS;
-    if (S < 1) S = 1;
-    int kp = (M + S - 1) / S;
-    kp = (kp + 63) / 64 * 64;
-    *splits = (M + kp - 1) / kp;
-    *kper = kp;
-    return;
-  }
-  if (wg_bias_fused(d)) {
-    const int ntile = 9 * ((d->Cout + 255) / 256) * ((d->Cin + 255) / 256);
-    int S = 256 / ntile;
-    const int maxS = (M + 255) / 256;
-    if (S > maxS) S = maxS;
-    if (S < 1) S = 1;
-    int kp = (M + S - 1) / S;
-    kp = (kp + 63) / 64 * 64;
-    *splits = (M + kp - 1) / kp;
-    *kper = kp;
-    return;
-  }
-  if (wg_bias_group(d) > 0) {  // pp kernel, bias-role blocks grouped (see conv3x3_wgrad_pp_kernel)
-    const int bg = wg_bias_group(d), tco = (d->Cout + 255) / 256;
-    const int ntile = 9 * tco * ((d->Cin + 255) / 256);
-    int S = (int)(256.0 / (ntile + (double)tco / bg));
-    while (S > 1 && S * ntile + (S + bg - 1) / bg * tco > 256) --S;
-    const int maxS = (M + 255) / 256;
-    if (S > maxS) S = maxS;
-    if (S < 1) S = 1;
-    int kp = (M + S - 1) / S;
-    kp = (kp + 63) / 64 * 64;
-    *splits = (M + kp - 1) / kp;
-    *kper = kp;
-    return;
-  }
-  if (wg_use_big(d)) {
-    bm = bn = 256;
-    target = 256;  // (512: 40.2 -> 41.7 ms EDSR step, round 2)
-    extra = (d->Cout + 255) / 256;
-  } else {
-    wg_tiles(d->Cout, d->Cin, &bm, &bn);
-    target = 1024;
-  }
+  if (wg_use_row3(d))  // 256 x 128 tiles, one kernel row (3 taps) per block
+    return plan_splits(M, one_wave_splits(3 * (d->Cout / 256) * (d->Cin / 128), d->Cout / 256, wg_row3_bg()), M / 64,
+                       splits, kper);
+  if (wg_bias_fused(d)) return plan_splits(M, 256 / (9 * tco * tci), (M + 255) / 256, splits, kper);
+  if (wg_bias_group(d) > 0)  // pp kernel, bias-role blocks grouped (see conv3x3_wgrad_pp_kernel)
+    return plan_splits(M, one_wave_splits(9 * tco * tci, tco, wg_bias_group(d)), (M + 255) / 256, splits, kper);
   const int taps = d->ksize == 1 ? 1 : 9;
-  const int tiles = taps * ((d->Cout + bm - 1) / bm) * ((d->Cin + bn - 1) / bn) + extra;
-  int S = extra ? target / tiles : (target + tiles / 2) / tiles;
-  const int maxS = (M + 255) / 256;  // at least 256 pixels per split
-  if (S > maxS) S = maxS;
-  if (S < 1) S = 1;
-  int kp = (M + S - 1) / S;
-  kp = (kp + 63) / 64 * 64;
-  S = (M + kp - 1) / kp;
-  *splits = S;
-  *kper = kp;
+  int S;
+  if (wg_use_big(d)) {  // ~1 round of 256 blocks (512: 40.2 -> 41.7 ms EDSR step, round 2), a bias-role block per co tile
+    S = 256 / (taps * tco * tci + tco);
+  } else {
+    int bm, bn;
+    wg_tiles(d->Cout, d->Cin, &bm, &bn);
+    const int tiles = taps * ((d->Cout + bm - 1) / bm) * ((d->Cin + bn - 1) / bn);
+    S = (1024 + tiles / 2) / tiles;
+  }
+  plan_splits(M, S, (M + 255) / 256, splits, kper);  // at least 256 pixels per split
 }
 
 // Shape / flag fields of FwdArgs from a descriptor (no pointers; validated by the caller).
@@ -5739,13 +5700,14 @@ int colsum_parts(const sr_conv3x3_desc* d, const FwdArgs& a0) {
   static float one;
   FwdArgs a = a0;
   a.colsum = &one;  // the kernel choice of a call that asks for the sums
-  if (d->out_ps || d->out_nchw || fwd_kind(a, d->dtype == SR_BF16) == FK_LIN) return 0;
-  if (fwd_kind(a, d->dtype == SR_BF16) == FK_BAND) {  // (rows or bands) x pixel waves
+  const FwdKind k = fwd_kind(a, d->dtype == SR_BF16);
+  if (d->out_ps || d->out_nchw || k == FK_LIN) return 0;
+  if (k == FK_BAND) {  // (rows or bands) x pixel waves
     const int rpb = band_cs_rows(a);
     return (rpb ? d->H / rpb : d->H) * (band_nwv(a) / (d->Cout / 32));
   }
   int rows, nt;
-  fwd_epi_geom(fwd_kind(a, d->dtype == SR_BF16), &rows, &nt);
+  fwd_epi_geom(k, &rows, &nt);
   const int HW = d->H * d->W;
   if (HW % rows) return 0;
   return HW / rows * (nt / 64);
@@ -5860,15 +5822,16 @@ int sr_conv3x3_fwd_colsum_parts(const sr_conv3x3_desc* d) {
 // descriptor (bench.py traces and rocprof summaries are matched on these names).
 const char* sr_conv3x3_fwd_kernel_name(const sr_conv3x3_desc* d) {
   const bool bf = d->dtype == SR_BF16;
-  switch (fwd_kind(fwd_shape(d), bf)) {
-    case FK_LIN: return lin_use_wk(fwd_shape(d)) ? "linear_wk_kernel" : "conv3x3_lin_kernel";
+  const FwdArgs a = fwd_shape(d);
+  switch (fwd_kind(a, bf)) {
+    case FK_LIN: return lin_use_wk(a) ? "linear_wk_kernel" : "conv3x3_lin_kernel";
     case FK_HALO: return "conv3x3_fwd_halo_kernel";
     case FK_BAND: return "conv3x3_fwd_band_kernel";
     case FK_TAIL: return "conv3x3_fwd_tail_kernel";
     case FK_BANDS: return "conv3x3_fwd_band_kernel";
     case FK_BIG: {
-      if (g_variant == 2) return "conv3x3_fwd_big_kernel";
-      return fwd_use_pph(fwd_shape(d)) || fwd_use_pph_strip(fwd_shape(d)) ? "conv3x3_fwd_pph_kernel" : "conv3x3_fwd_pp_kernel";
+      if (variant_is(SR_VARIANT_TWO_BARRIER)) return "conv3x3_fwd_big_kernel";
+      return fwd_use_pph(a) || fwd_use_pph_strip(a) ? "conv3x3_fwd_pph_kernel" : "conv3x3_fwd_pp_kernel";
     }
     case FK_256_16: return bf ? "conv3x3_fwd_kernel<bf16,256,16>" : "conv3x3_fwd_kernel<f32,256,16>";
     case FK_256_32: return bf ? "conv3x3_fwd_kernel<bf16,256,32>" : "conv3x3_fwd_kernel<f32,256,32>";
@@ -5892,14 +5855,14 @@ const char* sr_conv3x3_wgrad_kernel_name(const sr_conv3x3_wgrad_desc* d) {
   return d->dtype == SR_BF16 ? "conv3x3_wgrad_kernel<bf16>" : "conv3x3_wgrad_kernel<f32>";
 }
 
-// Kernel-variant switch for the parity tests' cross-checks: 0 = automatic, 1 = never a 256x256 kernel,
-// 2 = the two-barrier 256x256 kernels; the others each route one family to the kernel it replaced
-// (24, 28, 29, 33, 34, 35, 36, 37, 50, 55, 59, 61, 62, 63, 64, 67, 68, 76, 77, 78, 79, 80: see their sites above).  The
-// measured-slower paths and the timing ablations were removed in round 6 (git history).
+// Kernel-variant switch for the parity tests' cross-checks: an sr_conv_variant (include/sr_hip.h lists them, each
+// with the family it routes back to the kernel it replaced).  The measured-slower paths and the timing ablations
+// were removed in round 6 (git history).
 int sr_conv3x3_set_variant(int variant) {
-  static const int kValid[] = {0, 1, 2, 24, 28, 29, 33, 34, 35, 36, 37, 50, 55, 59, 61, 62, 63, 64, 67, 68, 76, 77, 78, 79, 80};
   bool ok = false;
-  for (int v : kValid) ok = ok || v == variant;
+#define SR_VARIANT_OK(name, value) ok = ok || variant == name;
+  SR_CONV_VARIANTS(SR_VARIANT_OK)
+#undef SR_VARIANT_OK
   if (!ok) return sr_fail(SR_EINVAL, "conv3x3_set_variant: not a parity cross-check variant");
   g_variant = variant;
   return SR_OK;
@@ -5953,6 +5916,8 @@ int wgrad_reduce_launch(const sr_conv3x3_wgrad_desc* d, int S, int taps, const f
   hipLaunchKernelGGL((wgrad_reduce_g_kernel<G, T, ##__VA_ARGS__>), grid, blk, (size_t)nw * 64 * 16, s, (const float*)ws, (const float*)wsb, dw, db, \
                      S, d->Cout, d->Cin, Cout_real, Cin_real, d->out_ps, taps, co_map, ci_map, d->scale, wblocks,  \
                      acc1)
+    // (the tr arm is never taken under the !tr guard above: the row-streaming slab keeps wgrad_reduce_tr_kernel; its
+    // three instantiations stay so that the set of kernels in the library is the parent's)
     if (tr) { if (gpw == 64) SR_RG(64, true); else if (gpw == 32) SR_RG(32, true); else SR_RG(16, true); }
     else if (cig) { if (gpw == 64) SR_RG(64, false, true); else if (gpw == 32) SR_RG(32, false, true); else SR_RG(16, false, true); }
     else { if (gpw == 64) SR_RG(64, false); else if (gpw == 32) SR_RG(32, false); else SR_RG(16, false); }
@@ -5971,7 +5936,7 @@ int wgrad_reduce_launch(const sr_conv3x3_wgrad_desc* d, int S, int taps, const f
     hipLaunchKernelGGL(wgrad_reduce4_kernel, dim3((unsigned)(wblocks + bblocks)), dim3(1024), 0, s, (const float*)ws,
                        (const float*)wsb, dw, db, S, d->Cout, d->Cin, Cout_real, Cin_real, d->out_ps, taps, co_map,
                        ci_map, d->scale, wblocks, acc1);
-  } else if (Cin_real <= 8 && g_variant != 33) {
+  } else if (Cin_real <= 8 && !variant_is(SR_VARIANT_REDUCE_PLAIN)) {
     hipLaunchKernelGGL(wgrad_reduce_narrow_kernel, dim3((unsigned)Cout_real), dim3(256), 0, s, (const float*)ws,
                        (const float*)wsb, dw, db, S, d->Cout, d->Cin, Cin_real, d->out_ps, taps, co_map, ci_map,
                        d->scale, acc1);
@@ -6050,25 +6015,14 @@ int sr_conv3x3_wgrad(const sr_conv3x3_wgrad_desc* d, const void* dy, const void*
   } else if (wg_use_big(d)) {
     a.tiles_co = (a.Cout + 255) / 256;
     a.tiles_ci = (a.Cin + 255) / 256;
-    const int per_split = taps * a.tiles_co * a.tiles_ci + (a.wsb ? a.tiles_co : 0);
-    a.bias_group = wg_bias_group(d);
     a.bias_fused = wg_bias_fused(d) ? 1 : 0;
-    if (a.bias_fused) {
-      a.bias_group = 0;
-      if (g_variant != 59)
-        hipLaunchKernelGGL((conv3x3_wgrad_pp_kernel<true>), dim3(S * taps * a.tiles_co * a.tiles_ci), dim3(512), 0, s, a);
-      else
-        hipLaunchKernelGGL(conv3x3_wgrad_pp_kernel<false>, dim3(S * taps * a.tiles_co * a.tiles_ci), dim3(512), 0, s, a);
-    } else if (a.bias_group > 0) {
-      const int nb = S * taps * a.tiles_co * a.tiles_ci + (a.wsb ? (S + a.bias_group - 1) / a.bias_group * a.tiles_co : 0);
-      if (g_variant != 59) hipLaunchKernelGGL((conv3x3_wgrad_pp_kernel<true>), dim3(nb), dim3(512), 0, s, a);
-      else hipLaunchKernelGGL(conv3x3_wgrad_pp_kernel<false>, dim3(nb), dim3(512), 0, s, a);
-    } else if (wg_use_pp(d) && g_variant != 59)
-      hipLaunchKernelGGL((conv3x3_wgrad_pp_kernel<true>), dim3(S * per_split), dim3(512), 0, s, a);
-    else if (wg_use_pp(d))
-      hipLaunchKernelGGL(conv3x3_wgrad_pp_kernel<false>, dim3(S * per_split), dim3(512), 0, s, a);
-    else
-      hipLaunchKernelGGL(conv3x3_wgrad_big_kernel, dim3(S * per_split), dim3(512), 0, s, a);
+    a.bias_group = a.bias_fused ? 0 : wg_bias_group(d);
+    // bias-role blocks per co tile: none (fused into the centre-tap blocks), one per bias_group splits, or one per split
+    const int bias_splits = a.bias_fused || !a.wsb ? 0 : a.bias_group > 0 ? (S + a.bias_group - 1) / a.bias_group : S;
+    const dim3 grid(S * taps * a.tiles_co * a.tiles_ci + bias_splits * a.tiles_co);
+    if (!wg_use_pp(d)) hipLaunchKernelGGL(conv3x3_wgrad_big_kernel, grid, dim3(512), 0, s, a);
+    else if (variant_is(SR_VARIANT_FOUR_PHASE)) hipLaunchKernelGGL(conv3x3_wgrad_pp_kernel<false>, grid, dim3(512), 0, s, a);
+    else hipLaunchKernelGGL(conv3x3_wgrad_pp_kernel<true>, grid, dim3(512), 0, s, a);
     e = hipGetLastError();
   } else {
     e = d->dtype == SR_BF16 ? dispatch_wg<bf16_t>(a, s) : dispatch_wg<float>(a, s);

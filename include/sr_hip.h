@@ -134,8 +134,40 @@ const char* sr_conv3x3_wgrad_kernel_name(const struct sr_conv3x3_wgrad_desc* d);
  * output slices of the sliced band form) -- the per-launch unit of traces and profiler summaries. */
 int sr_conv3x3_fwd_launches(const sr_conv3x3_desc* d);
 
-/* Kernel-variant selection for A/B tests: 0 = automatic (default), 1 = never use the
- * 256x256 LDS-DMA kernel (all shapes on the 128-row register-staged kernels). */
+/* Kernel-variant switch for the parity tests' cross-checks and A/B timing: 0 = automatic (default); every
+ * other value routes one kernel family back to the kernel it replaced.  The one list of accepted values:
+ * X(name, value), also what sr_conv3x3_set_variant validates against (basicsr4rs_amd/_lib.py mirrors it). */
+#define SR_CONV_VARIANTS(X)                                                                                             \
+  X(SR_VARIANT_AUTO, 0)                /* automatic selection */                                                        \
+  X(SR_VARIANT_TILE_ONLY, 1)           /* every family -> the register-staged tile kernels (no 256x256, halo, band, lin, tail, ring, linear_wgrad) */ \
+  X(SR_VARIANT_TWO_BARRIER, 2)         /* 256x256 forward and wgrad -> the two-barrier kernels (the previous schedule) */ \
+  X(SR_VARIANT_NO_PPH, 24)             /* forward pph (halo rows, strips) -> the per-tap pp kernel */                   \
+  X(SR_VARIANT_WG_NO_PARTIAL, 28)      /* wgrad pp with partial tiles and the kernel-row wgrad -> the 128x128 tile kernel */ \
+  X(SR_VARIANT_NO_TAIL, 29)            /* HR tail convs (Cout <= 16, NCHW store): tail / W-256 halo kernel -> the tile kernel */ \
+  X(SR_VARIANT_REDUCE_PLAIN, 33)       /* narrow-Cin slab reduce (block per channel) -> the one-thread-per-weight reduce */ \
+  X(SR_VARIANT_NO_BAND, 34)            /* band kernel (whole rows, strips, slices) -> the tile kernel */                \
+  X(SR_VARIANT_BAND_64, 35)            /* band kernel on 64 blocks: long bands that wrap the ring and cross images */   \
+  X(SR_VARIANT_BAND_256, 36)           /* automatic; the band tests' name for the default 256-block grid */             \
+  X(SR_VARIANT_BAND_CS_ROWS, 37)       /* band channel sums per row -> not reduced over the band */                     \
+  X(SR_VARIANT_PPH_NO_PS, 50)          /* pixel-shuffled input: pph -> the pp kernel */                                 \
+  X(SR_VARIANT_LIN_WIDE_BIG, 55)       /* linears with 192 < K <= 576: 64-token lin kernel -> the 256x256 pp kernel */  \
+  X(SR_VARIANT_FOUR_PHASE, 59)         /* two-interval pph forward and wgrad pp -> their 4-phase forms */               \
+  X(SR_VARIANT_PPH_P2_1, 61)           /* pph two-interval schedule without the B prefetch two K-steps ahead */         \
+  X(SR_VARIANT_RING_WIDE_ALL, 62)      /* every bf16 3x3 wgrad with Cout > 64 -> the ring kernel over 64-co tiles */    \
+  X(SR_VARIANT_NO_LINEAR_WGRAD, 63)    /* 1x1 wgrad: linear_wgrad_kernel -> the pp kernel */                            \
+  X(SR_VARIANT_NO_LINEAR_WK, 64)       /* linears: linear_wk_kernel -> the lin kernel */                                \
+  X(SR_VARIANT_RING_NO_PS, 67)         /* pixel-shuffled dy: ring wgrad over 64-co tiles -> pp / tile kernels */        \
+  X(SR_VARIANT_HALO_NO_PS, 68)         /* pixel-shuffled input: halo kernel -> the tile kernel */                       \
+  X(SR_VARIANT_NO_BAND_STRIP, 76)      /* band kernel over 128-px column strips -> the tile kernel */                   \
+  X(SR_VARIANT_NO_PPH_STRIP, 77)       /* pph over 64-px column strips -> the pp kernel */                              \
+  X(SR_VARIANT_NO_ROW3, 78)            /* kernel-row wgrad -> the pp kernel */                                          \
+  X(SR_VARIANT_NO_BIG_PARTIAL, 79)     /* 128 < Cout < 256 from Cin >= 128: pph with a partial tile -> the halo kernel */ \
+  X(SR_VARIANT_PPH_ONE_TILE, 80)       /* persistent multi-tile pph -> its one-tile form */
+enum sr_conv_variant {
+#define SR_VARIANT_ENUM(name, value) name = value,
+  SR_CONV_VARIANTS(SR_VARIANT_ENUM)
+#undef SR_VARIANT_ENUM
+};
 int sr_conv3x3_set_variant(int variant);
 int sr_conv3x3_get_variant(void); /* the current kernel-variant switch */
 /* Diagnostics (not part of the reference interface): per-block clock stamps of the row-band
