@@ -112,6 +112,9 @@ SIGNATURES = {
     'sr_convk_wgrad_workspace': (_sz, [ctypes.POINTER(ConvKDesc)]),
     'sr_convk_wgrad': (_i, [ctypes.POINTER(ConvKDesc), _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     'sr_bicubic_up': (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    'sr_bicubic_up_hp': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    'sr_val_metrics_workspace': (_sz, [_i, _i, _i, _i, _i]),
+    'sr_val_metrics': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     'sr_nchw_to_nhwc': (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'sr_nhwc_to_nchw': (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'sr_pixel_shuffle_nchw': (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -7,6 +7,8 @@
 //                   reduced in a fixed order (no atomics: two runs are bit-identical).
 //   sr_bicubic_up   F.interpolate(mode='bicubic', align_corners=True) by an integer scale, fp32 NCHW in,
 //                   NHWC feature map out.
+//   sr_bicubic_up_hp  the align_corners=False form, fp32 NCHW in and out, written into a channel range
+//                   of a wider tensor (the ground-truth assembly of L2SSingleModel.feed_data).
 //
 // Forward.  A block of 4 waves owns a TH x TW tile of output pixels of ONE image and stages the tile
 // plus its k - 1 halo of x in LDS once; pixels outside the image are written as zeros there, so no
@@ -421,6 +423,52 @@ __global__ void bicubic_up_kernel(const float* __restrict__ x, int N, int C, int
   y[i] = Elt<T>::from_f(v);
 }
 
+// Bicubic upsampling, align_corners = False ("half-pixel" centres, F.interpolate's default): source
+// coordinate (d + 0.5) / s - 0.5, not clamped; its floor and fraction t; the same A = -0.75 weights and
+// clamped taps.  With an integer scale d = q * s + p gives the coordinate q + f, f = (p + 0.5) / s - 0.5
+// in (-0.5, 0.5): floor q - 1 and t = f + 1 for f < 0, else floor q and t = f -- t is a function of the
+// phase p alone and is formed from small integers, so it carries no error that grows with d.
+// fp32 NCHW in, fp32 NCHW out into channels [c0, c0 + C) of a [N, Cy, H s, W s] tensor (a fused cat).
+SR_DEV void hp_phase(int d, int s, int& i0, float (&c)[4]) {
+  const int q = d / s, p = d - q * s;
+  const float f = ((float)p + 0.5f) / (float)s - 0.5f;
+  i0 = f < 0.f ? q - 1 : q;
+  cubic_coeffs(f < 0.f ? f + 1.f : f, c);
+}
+
+__global__ void bicubic_up_hp_kernel(const float* __restrict__ x, int N, int C, int H, int W, int s,
+                                     float* __restrict__ y, int Cy, int c0) {
+  const int Ho = H * s, Wo = W * s;
+  const int64_t total = (int64_t)N * C * Ho * Wo;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int ox = (int)(i % Wo);
+  int64_t p = i / Wo;
+  const int oy = (int)(p % Ho);
+  p /= Ho;
+  const int c = (int)(p % C);
+  const int n = (int)(p / C);
+  int iy, ix;
+  float cy[4], cx[4];
+  hp_phase(oy, s, iy, cy);
+  hp_phase(ox, s, ix, cx);
+  const float* plane = x + ((size_t)n * C + c) * (size_t)H * W;
+  float v = 0.f;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int yy = min(max(iy - 1 + r, 0), H - 1);
+    const float* row = plane + (size_t)yy * W;
+    float h = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int xx = min(max(ix - 1 + q, 0), W - 1);
+      h += row[xx] * cx[q];
+    }
+    v += h * cy[r];
+  }
+  y[(((size_t)n * Cy + c0 + c) * Ho + oy) * (size_t)Wo + ox] = v;
+}
+
 int lds_pixel_stride(int channels, int size) {
   const int b = channels * size;
   return b % 64 == 0 ? b + 16 : b;
@@ -563,6 +611,20 @@ int sr_bicubic_up(int dtype, const float* x, int N, int C, int H, int W, int s, 
     hipLaunchKernelGGL(bicubic_up_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, x, N, C, H, W, s, Cp,
                        (float*)y);
   return sr_check(hipGetLastError(), "bicubic_up launch");
+}
+
+int sr_bicubic_up_hp(const float* x, int N, int C, int H, int W, int s, float* y, int Cy, int c0, void* stream) {
+  if (!x || !y) return sr_fail(SR_EINVAL, "bicubic_up_hp: null pointer");
+  if (N < 1 || C < 1 || H < 1 || W < 1 || s < 1) return sr_fail(SR_EINVAL, "bicubic_up_hp: bad shape");
+  if (c0 < 0 || (int64_t)c0 + C > Cy) return sr_fail(SR_EINVAL, "bicubic_up_hp: channels [c0, c0 + C) must lie in [0, Cy)");
+  if ((int64_t)H * s > 0x7fffffff || (int64_t)W * s > 0x7fffffff) return sr_fail(SR_ETOOBIG, "bicubic_up_hp: output too large");
+  const int64_t plane = (int64_t)H * s * W * s;
+  if (plane > INT64_MAX / N / C) return sr_fail(SR_ETOOBIG, "bicubic_up_hp: output too large");
+  const int64_t blocks = (plane * N * C + 255) / 256;
+  if (blocks > 0x7fffffff) return sr_fail(SR_ETOOBIG, "bicubic_up_hp: output too large");
+  hipLaunchKernelGGL(bicubic_up_hp_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, N, C, H, W, s, y,
+                     Cy, c0);
+  return sr_check(hipGetLastError(), "bicubic_up_hp launch");
 }
 
 }  // extern "C"

@@ -154,3 +154,36 @@ def calculate_ssim_pt(img, img2, crop_border, test_y_channel=False, **kwargs):
     img = img.to(torch.float64)
     img2 = img2.to(torch.float64)
     return _ssim_pth(img * 255., img2 * 255.)
+
+
+def _select_band(img, img2, band, input_order):
+    """One band of both images, still 2-D (psnr_ssim.py:67-77, 186-196)."""
+    assert img.shape == img2.shape, f'Image shapes are different: {img.shape}, {img2.shape}.'
+    if input_order == 'HWC':
+        assert band < img.shape[2], f'Band index {band} out of range for shape {img.shape}.'
+        return img[:, :, band], img2[:, :, band]
+    if input_order == 'CHW':
+        assert band < img.shape[0], f'Band index {band} out of range for shape {img.shape}.'
+        return img[band, :, :], img2[band, :, :]
+    raise ValueError(f'Wrong input_order {input_order}. Supported input_orders are "HWC" and "CHW".')
+
+
+@METRIC_REGISTRY.register()
+def calculate_psnr_band(img, img2, crop_border, band, input_order='HWC', test_y_channel=False, **kwargs):
+    """calculate_psnr of one band (psnr_ssim.py:51-88): the band is cut out, given back its channel axis
+    in ``input_order`` and handed to calculate_psnr with ``test_y_channel`` forwarded."""
+    b1, b2 = _select_band(img, img2, band, input_order)
+    axis = 2 if input_order == 'HWC' else 0
+    return calculate_psnr(np.expand_dims(b1, axis), np.expand_dims(b2, axis), crop_border, input_order=input_order,
+                          test_y_channel=test_y_channel, **kwargs)
+
+
+@METRIC_REGISTRY.register()
+def calculate_ssim_band(img, img2, crop_border, band, input_order='HWC', **kwargs):
+    """The single-channel SSIM of one band (psnr_ssim.py:171-206).  No ``test_y_channel`` parameter: a
+    configured key lands in ``kwargs`` and is not applied, as in the reference."""
+    b1, b2 = _select_band(img, img2, band, input_order)
+    if crop_border != 0:
+        b1 = b1[crop_border:-crop_border, crop_border:-crop_border]
+        b2 = b2[crop_border:-crop_border, crop_border:-crop_border]
+    return _ssim(b1.astype(np.float64), b2.astype(np.float64))

@@ -11,6 +11,10 @@ Validation (srrs_model.py:93-138) works on tensors in [-1, 1]: every visual goes
 order kept), the metrics compare the ``sr`` and ``gt`` images, each image's scores go into a
 per-image table written as ``<visualization>/<dataset>_<iter>.csv`` (srrs_model.py:214-216), and
 saved visuals are split into RGB (channels 0-2) and NIR (channel 3) PNGs (srrs_model.py:194-212).
+
+``val.device_metrics: true`` (default false) takes the PSNR / SSIM scores from the ``sr_val_metrics``
+HIP kernel on the device tensors instead (ops/metrics.py): the same table, PSNR exactly and SSIM to
+1e-10, without bringing the images to the host unless they are saved.
 """
 import os
 from collections import OrderedDict
@@ -21,7 +25,9 @@ import torch
 
 from ..metrics import calculate_metric
 from ..ops.conv import async_wgrad
+from ..ops.metrics import DEVICE_METRICS, scores_from_device
 from ..utils.img_util import imwrite, minusone_one_tensor_to_ubyte_numpy
+from ..utils.logger import get_root_logger
 from ..utils.registry import MODEL_REGISTRY
 from .sr_model import SRModel
 
@@ -91,11 +97,25 @@ class SRRSModel(SRModel):
         if metrics_enabled:
             self._prepare_metrics(dataset_name)
         detailed = pd.DataFrame()  # one row per image, one column per metric (srrs_model.py:101)
+        on_device = metrics_enabled and bool(self.opt['val'].get('device_metrics', False))
         idx = -1
         for idx, val_data in enumerate(dataloader):
             img_name = self._extract_img_name(val_data)
             self.feed_data(val_data)
             self.test()
+            if on_device and self._device_metrics_ok():
+                # val.device_metrics: the scores come from one HIP kernel on the device tensors; the
+                # images leave the device only to be saved
+                self._compute_metrics_device(img_name, self.output, self.gt, detailed)
+                converted = {}
+                if save_img:
+                    visuals = self.get_current_visuals(current_iter)
+                    converted = {k: minusone_one_tensor_to_ubyte_numpy(v) for k, v in visuals.items()
+                                 if v is not None and k != 'sr'}
+                self._release_gpu_memory()
+                if save_img:
+                    self._save_visuals(dataset_name, img_name, converted)
+                continue
             visuals = self.get_current_visuals(current_iter)
             converted = {k: minusone_one_tensor_to_ubyte_numpy(v) for k, v in visuals.items() if v is not None}
             self._release_gpu_memory()
@@ -131,6 +151,43 @@ class SRRSModel(SRModel):
             return
         data = {'img': sr_img, 'img2': gt_img}
         scores = {name: calculate_metric(data, opt_) for name, opt_ in self.opt['val']['metrics'].items()}
+        for name, score in scores.items():
+            detailed.loc[img_name, name] = score
+            self.metric_results[name] += score
+
+    def _device_metrics_ok(self):
+        """Whether this image's scores can come from ``sr_val_metrics`` (val.device_metrics).  The
+        kernel stands in for calculate_psnr / calculate_ssim and their ``_band`` forms without the Y
+        channel, on one image of at least two channels (the host conversion repeats a single channel
+        to three, utils/img_util.py:make_grid); anything else takes the host path whole, with one
+        warning per reason."""
+        reason = None
+        for name, o in self.opt['val']['metrics'].items():
+            if o.get('type') not in DEVICE_METRICS:
+                reason = f'metric {name!r} is {o.get("type")}'
+            elif o.get('test_y_channel', False):
+                reason = f'metric {name!r} sets test_y_channel'
+            if reason:
+                break
+        if reason is None:
+            if not hasattr(self, 'gt'):
+                reason = 'the batch has no gt'
+            elif self.output.dim() != 4 or self.output.shape != self.gt.shape:
+                reason = f'sr {tuple(self.output.shape)} and gt {tuple(self.gt.shape)} differ in shape'
+            elif self.output.shape[0] != 1:
+                reason = f'the validation batch is {self.output.shape[0]}, not 1'
+            elif self.output.shape[1] < 2:
+                reason = 'the images have one channel'
+        if reason is None:
+            return True
+        warned = self.__dict__.setdefault('_device_metrics_warned', set())
+        if reason not in warned:
+            warned.add(reason)
+            get_root_logger().warning(f'val.device_metrics: host metrics instead ({reason})')
+        return False
+
+    def _compute_metrics_device(self, img_name, sr, gt, detailed):
+        scores = scores_from_device(self.opt['val']['metrics'], sr, gt)
         for name, score in scores.items():
             detailed.loc[img_name, name] = score
             self.metric_results[name] += score

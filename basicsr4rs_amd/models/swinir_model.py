@@ -6,6 +6,7 @@ from torch.nn import functional as F
 
 from ..utils.registry import MODEL_REGISTRY
 from .sr_model import SRModel
+from .srrs_l2s_model import L2SSingleModel
 from .srrs_model import SRRSModel
 
 
@@ -32,4 +33,10 @@ class SwinIRModel(SRModel):
 
 @MODEL_REGISTRY.register()
 class SwinIRRSModel(SwinIRModel, SRRSModel):
+    pass
+
+
+@MODEL_REGISTRY.register()
+class SwinIRL2sModel(SwinIRModel, L2SSingleModel):
+    """basicsr/models/swinir_model.py:45-47: SwinIRModel's padded ``test`` on L2SSingleModel's batches."""
     pass

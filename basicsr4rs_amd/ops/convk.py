@@ -7,6 +7,9 @@ come from ``prepared_images`` (so ``refresh_prepared`` keeps them current after 
 step, also inside a captured step), and the weight gradient lands in the FlatParams gradient views
 through ``grad_target`` / ``grad_ready``.  The weight gradient always runs on the current stream: with
 ``async_wgrad`` of any mode the results are the synchronous ones.
+
+``bicubic_up_hp`` is the ``align_corners=False`` upsampler of L2SSingleModel.feed_data (fp32 NCHW in and
+out, optionally into a channel range of a wider tensor).
 """
 import torch
 
@@ -167,3 +170,35 @@ def bicubic_up(x, scale, dtype, cp=None):
     else:
         _lib.check(lib.sr_bicubic_up(*args))
     return y
+
+
+def bicubic_up_hp(x, scale, out=None, c0=0):
+    """F.interpolate(x, scale_factor=scale, mode='bicubic') (align_corners=False) of an fp32 NCHW tensor by
+    an integer scale, fp32 NCHW out.  With ``out`` [N, Cy, H*scale, W*scale] (fp32, contiguous) the result
+    is written into its channels [c0, c0 + C) and the others are left alone (a fused ``torch.cat``).
+    The gradient with respect to the image is not implemented."""
+    if x.requires_grad:
+        raise NotImplementedError('bicubic_up_hp: the gradient with respect to the input image is not implemented '
+                                  '(pass a tensor that does not require grad)')
+    if int(scale) != scale or scale < 1:
+        raise ValueError(f'bicubic_up_hp: integer scale >= 1, got {scale}')
+    scale = int(scale)
+    N, Cc, H, W = x.shape
+    xc = x.detach().contiguous().float()
+    if out is None:
+        out = torch.empty(N, Cc, H * scale, W * scale, device=x.device, dtype=torch.float32)
+        c0 = 0
+    elif (out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 4 or out.device != x.device
+          or (out.shape[0], out.shape[2], out.shape[3]) != (N, H * scale, W * scale)):
+        raise ValueError(f'bicubic_up_hp: out must be a contiguous fp32 [{N}, Cy, {H * scale}, {W * scale}] tensor on '
+                         f'{x.device}, got {out.dtype} {tuple(out.shape)}')
+    lib = _lib.load()
+    args = (_lib.ptr(xc), N, Cc, H, W, scale, _lib.ptr(out), out.shape[1], int(c0), _lib.stream())
+    if ktrace.active():
+        keep = (xc, out)
+        with ktrace.span('bicubic_up_hp_kernel', 32.0 * xc.numel() * scale * scale, 4 * xc.numel() * (1 + scale * scale),
+                         relaunch=lambda a=args, kp=keep: lib.sr_bicubic_up_hp(*a[:-1], _lib.stream())):
+            _lib.check(lib.sr_bicubic_up_hp(*args))
+    else:
+        _lib.check(lib.sr_bicubic_up_hp(*args))
+    return out

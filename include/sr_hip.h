@@ -274,6 +274,29 @@ int sr_convk_wgrad(const sr_convk_desc* d, const void* dy, const void* x, void* 
  * coordinate o*(in-1)/(out-1), A = -0.75, clamped taps, fp32 arithmetic), layout change fused:
  * fp32 NCHW [N,C,H,W] -> NHWC dtype [N,H*s,W*s,Cp] (channels >= C zero). */
 int sr_bicubic_up(int dtype, const float* x, int N, int C, int H, int W, int s, int Cp, void* y, void* stream);
+/* Bicubic upsampling by an integer scale s >= 1 with torch's align_corners=False semantics (source
+ * coordinate (o + 0.5) / s - 0.5, not clamped; A = -0.75, clamped taps, fp32 arithmetic): fp32 NCHW
+ * [N,C,H,W] -> channels [c0, c0 + C) of the fp32 NCHW tensor y [N,Cy,H*s,W*s]; the other channels of y
+ * are not touched (a fused torch.cat).  SR_EINVAL unless 0 <= c0 and c0 + C <= Cy. */
+int sr_bicubic_up_hp(const float* x, int N, int C, int H, int W, int s, float* y, int Cy, int c0, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Validation metrics (csrc/metrics.hip): PSNR / SSIM inputs of metrics/psnr_ssim.py computed on the
+ * device.  sr, gt: fp32 NCHW [N,C,H,W] in nominal [-1, 1].  Both are quantised to ubyte as
+ * minusone_one_tensor_to_ubyte_numpy does (clamp, (t + 1) / 2, * 255 in fp32, round half to even,
+ * clip; bit-identical to the host), `crop` pixels are dropped on each edge, and per (n, c):
+ *   sse[n*C + c]   the exact integer sum of squared ubyte differences over the crop
+ *                  (PSNR = 10 log10(255^2 n / sse) on the host);
+ *   ssim[n*C + c]  the mean of the 11-tap Gaussian (sigma 1.5) valid-mode SSIM map in float64
+ *                  (C1 = (0.01*255)^2, C2 = (0.03*255)^2); NaN when the crop is smaller than 11 x 11.
+ * Per-tile partials go to a workspace of sr_val_metrics_workspace(...) bytes (8-byte aligned) and are
+ * reduced in a fixed order: no atomics, two runs are bit-identical.  SR_EINVAL for null pointers,
+ * non-positive sizes, crop < 0, 2 * crop >= min(H, W) or a workspace that is too small (the size
+ * query then returns 0).
+ * ------------------------------------------------------------------------------- */
+size_t sr_val_metrics_workspace(int N, int C, int H, int W, int crop);
+int sr_val_metrics(const float* sr, const float* gt, int N, int C, int H, int W, int crop, int64_t* sse, double* ssim,
+                   void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Layout / elementwise ops (HBM-bound).
