@@ -17,6 +17,9 @@ LIB_PATH = switch('SR_HIP_LIB') or os.path.join(os.path.dirname(os.path.abspath(
 
 SR_F32, SR_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
+# enum sr_loss_kind / sr_loss_reduction
+LOSS_L1, LOSS_MSE, LOSS_CHARBONNIER = 0, 1, 2
+REDUCE_NONE, REDUCE_MEAN, REDUCE_SUM = 0, 1, 2
 
 # sr_conv3x3_set_variant values: enum sr_conv_variant of include/sr_hip.h (there with what each reroutes)
 SR_VARIANT_AUTO = 0
@@ -120,6 +123,8 @@ SIGNATURES = {
     'sr_pixel_shuffle_nchw': (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'sr_l1_loss': (_i, [_vp, _vp, _i64, _f, _i, _vp, _vp, _vp, _sz, _vp]),
     'sr_l1_loss_workspace': (_sz, [_i64]),
+    'sr_pixel_loss': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sr_pixel_loss_workspace': (_sz, [_i64]),
     'sr_act_backward': (_i, [_i, _vp, _vp, _i64, _i, _f, _f, _vp, _vp]),
     'sr_row_scale': (_i, [_i, _vp, _i64, _i, _i, _vp, _vp, _vp]),
     'sr_adam_ema': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _vp]),

@@ -5018,18 +5018,6 @@ bool fwd_use_pph(const FwdArgs& a) {
          (a.in_ps == 0 || (a.fd_cps.d % 64 == 0 && !variant_is(SR_VARIANT_PPH_NO_PS))) && a.in_up == 1 && a.tap0 == 0;
 }
 
-// Compute units of the current device, queried once per device (the persistent pph grid)
-int device_cus() {
-  static std::atomic<int> cus[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  int n = cus[dev].load(std::memory_order_relaxed);
-  if (n <= 0) {
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus[dev].store(n, std::memory_order_relaxed);
-  }
-  return n;
-}
 // Grid of the persistent multi-tile form of the pph kernel (conv3x3_fwd_pph_kernel<4, 2, false, true>), 0:
 // the one-tile form.  W 64 whole-row tiles (fwd_use_pph), Cout 256 (one full column tile), plain NHWC input and output,
 // bias / activation / alpha and at most ONE of gate (modes 0, 1) and residual -- the EDSR / RCAN-style
@@ -5040,7 +5028,7 @@ int pph_pers_grid(const FwdArgs& a) {
   if (variant_is(SR_VARIANT_PPH_ONE_TILE) || a.W != 64 || a.Cout != 256 || a.tiles_n != 1 || a.in_ps != 0 || a.out_ps != 0 || a.colsum || a.out_nchw ||
       a.aux || a.res2 || a.row_scale || a.dot || (a.gate && a.res) || (a.gate && a.gate_mode == 2) || a.M % 256)
     return 0;
-  const int G = sr_knob(K_PPH_GRID) > 0 ? sr_knob(K_PPH_GRID) : device_cus();
+  const int G = sr_knob(K_PPH_GRID) > 0 ? sr_knob(K_PPH_GRID) : sr_device_cus();
   return a.tiles > G ? G : 0;
 }
 

@@ -20,6 +20,20 @@ int sr_check(hipError_t e, const char* what) {
   return SR_ELAUNCH;
 }
 
+// Compute units of the current device, queried once per device (256 when there is none to ask): the
+// grids of the persistent pph forward and of the streaming loss kernels
+int sr_device_cus() {
+  static std::atomic<int> cus[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+  int n = cus[dev].load(std::memory_order_relaxed);
+  if (n <= 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+
 // Tuning knobs (A/B switches and plan targets).  Each is read from its environment variable ONCE
 // per process (the library's only getenv site) and can be overridden at run time by sr_set_knob;
 // kernels read the cached value (no per-call environment lookups).  -1 = unset (the built-in default).

@@ -5,6 +5,8 @@
 
 int sr_fail(int code, const char* msg);
 int sr_check(hipError_t e, const char* what);
+// compute units of the current device (cached per device)
+int sr_device_cus();
 
 // Tuning knobs (sr_core.hip): environment variable of the same name read once per process,
 // overridable by sr_set_knob; -1 = unset.

@@ -2,9 +2,9 @@
 from copy import deepcopy
 
 from ..utils.registry import LOSS_REGISTRY
-from .basic_loss import L1Loss
+from .basic_loss import CharbonnierLoss, L1Loss, MSELoss, WeightedTVLoss
 
-__all__ = ['build_loss', 'L1Loss']
+__all__ = ['build_loss', 'L1Loss', 'MSELoss', 'CharbonnierLoss', 'WeightedTVLoss']
 
 
 def build_loss(opt):

@@ -1,9 +1,13 @@
-"""Pixel losses (mirror of basicsr/losses/basic_loss.py:12-114, loss_util.py:6-96).
+"""Pixel losses (mirror of basicsr/losses/basic_loss.py:12-143, loss_util.py:6-96).
 
 L1Loss with reduction 'mean'/'sum' and no weight map — the configuration of every SR
 train YAML on the hot path (e.g. options/train/EDSR/train_EDSR_Lx4.yml ``pixel_opt``) — is
-one fused HIP reduction that also writes the gradient (sr_l1_loss).  Weighted or
-reduction='none' variants use plain torch ops on the device tensors.
+one fused HIP reduction that also writes the gradient (sr_l1_loss).  Everything else of the
+family — MSELoss, CharbonnierLoss, a per-pixel weight map ([N,1,H,W] or [N,C,H,W]),
+reduction='none', bf16 predictions, WeightedTVLoss — runs on the streaming kernels of
+csrc/loss.hip (sr_pixel_loss): one pass over pred / target that writes the gradient, plus a
+weight-sum pass for the weighted mean.  Only a weight map that itself requires grad, or one of
+another shape, goes through plain torch ops with the reference's formula.
 """
 import torch
 from torch import nn as nn
@@ -12,6 +16,8 @@ from .. import _lib
 from ..utils.registry import LOSS_REGISTRY
 
 _reduction_modes = ['none', 'mean', 'sum']
+_REDUCE = {'none': _lib.REDUCE_NONE, 'mean': _lib.REDUCE_MEAN, 'sum': _lib.REDUCE_SUM}
+_CPU_MESSAGE = 'basicsr4rs_amd losses run on the MI355X device'
 
 
 class _L1Fused(torch.autograd.Function):
@@ -38,28 +44,155 @@ class _L1Fused(torch.autograd.Function):
         return grad * g, None, None, None
 
 
+class _PixelLossFused(torch.autograd.Function):
+    """sr_pixel_loss: the loss (a fp32 scalar, or the elementwise map of reduction 'none' in pred's
+    dtype) and d loss / d pred from one pass; d loss / d target is its negation."""
+
+    @staticmethod
+    def forward(ctx, pred, target, weight, kind, reduction, loss_weight, eps):
+        if pred.dtype not in (torch.float32, torch.bfloat16):
+            pred = pred.float()
+        if target.dtype != torch.float32 and target.dtype != pred.dtype:
+            target = target.float()
+        pred, target = pred.contiguous(), target.contiguous()
+        if weight is not None:
+            weight = weight.detach().float().contiguous()
+        lib = _lib.load()
+        # without a weight map the layout does not matter: any shape is one row of numel() elements
+        N, C, H, W = pred.shape if pred.dim() == 4 else (1, 1, 1, pred.numel())
+        ws_bytes = lib.sr_pixel_loss_workspace(pred.numel())
+        ws = torch.empty(ws_bytes // 8 + 1, device=pred.device, dtype=torch.float64)
+        none = reduction == 'none'
+        loss = None if none else torch.empty((), device=pred.device, dtype=torch.float32)
+        out = torch.empty_like(pred) if none else None
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        grad = torch.empty_like(pred) if need else None
+        _lib.check(
+            lib.sr_pixel_loss(kind, _REDUCE[reduction], _lib.dtype_code(pred.dtype), _lib.dtype_code(target.dtype),
+                              _lib.ptr(pred), _lib.ptr(target), _lib.ptr(weight),
+                              0 if weight is None else weight.size(1), N, C, H, W, float(loss_weight), float(eps),
+                              _lib.ptr(loss), _lib.ptr(out), _lib.ptr(grad), _lib.ptr(ws), ws_bytes, _lib.stream()))
+        ctx.save_for_backward(grad)
+        ctx.target_dtype = target.dtype
+        return out if none else loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad, ) = ctx.saved_tensors
+        # g: the upstream scalar, or the upstream map of reduction 'none'; the product in pred's dtype
+        gp = (grad * g).to(grad.dtype)
+        gt = (-gp).to(ctx.target_dtype) if ctx.needs_input_grad[1] else None
+        return (gp if ctx.needs_input_grad[0] else None), gt, None, None, None, None, None
+
+
+def _elementwise(kind, pred, target, eps):
+    if kind == _lib.LOSS_L1:
+        return (pred - target).abs()
+    if kind == _lib.LOSS_MSE:
+        return (pred - target)**2
+    return torch.sqrt((pred - target)**2 + eps)
+
+
+def _torch_pixel_loss(kind, pred, target, weight, reduction, loss_weight, eps):
+    """The reference's formula (weight_reduce_loss, loss_util.py:26-55) in torch ops on the device
+    tensors: a weight map that requires grad, or one the kernel's two layouts do not cover."""
+    loss = _elementwise(kind, pred, target, eps)
+    if weight is not None:
+        assert weight.dim() == loss.dim()
+        assert weight.size(1) == 1 or weight.size(1) == loss.size(1)
+        loss = loss * weight
+    if reduction == 'sum':
+        loss = loss.sum()
+    elif reduction == 'mean':
+        if weight is None:
+            loss = loss.mean()
+        else:
+            loss = loss.sum() / (weight.sum() if weight.size(1) > 1 else weight.sum() * loss.size(1))
+    return loss_weight * loss
+
+
+def _pixel_loss(kind, pred, target, weight, reduction, loss_weight, eps=0.0):
+    if not pred.is_cuda:
+        raise NotImplementedError(_CPU_MESSAGE)
+    if weight is None and kind == _lib.LOSS_L1 and reduction in ('mean', 'sum') and not target.requires_grad:
+        return _L1Fused.apply(pred, target, loss_weight, reduction == 'mean')
+    # sizes are C ints: a tensor that is not 4-D travels as one row of numel() elements
+    kernel_ok = pred.shape == target.shape and 0 < pred.numel() < (2**32 - 9 if pred.dim() == 4 else 2**31)
+    if weight is not None:
+        kernel_ok = (kernel_ok and not weight.requires_grad and pred.dim() == 4 and weight.dim() == 4
+                     and weight.size(1) in (1, pred.size(1)) and weight.size(0) == pred.size(0)
+                     and weight.shape[2:] == pred.shape[2:])
+    if not kernel_ok:
+        return _torch_pixel_loss(kind, pred, target, weight, reduction, loss_weight, eps)
+    return _PixelLossFused.apply(pred, target, weight, kind, reduction, loss_weight, eps)
+
+
+def _check_reduction(reduction):
+    if reduction not in _reduction_modes:
+        raise ValueError(f'Unsupported reduction mode: {reduction}. Supported ones are: {_reduction_modes}')
+
+
 @LOSS_REGISTRY.register()
 class L1Loss(nn.Module):
     """L1 (mean absolute error, MAE) loss (basic_loss.py:27-52)."""
 
     def __init__(self, loss_weight=1.0, reduction='mean'):
         super().__init__()
-        if reduction not in _reduction_modes:
-            raise ValueError(f'Unsupported reduction mode: {reduction}. Supported ones are: {_reduction_modes}')
+        _check_reduction(reduction)
         self.loss_weight = loss_weight
         self.reduction = reduction
 
     def forward(self, pred, target, weight=None, **kwargs):
-        if weight is None and self.reduction in ('mean', 'sum') and pred.is_cuda:
-            return _L1Fused.apply(pred, target, self.loss_weight, self.reduction == 'mean')
-        if not pred.is_cuda:
-            raise NotImplementedError('basicsr4rs_amd losses run on the MI355X device')
-        loss = (pred - target).abs()
-        if weight is not None:
-            loss = loss * weight
-        if self.reduction == 'mean':
-            # weight_reduce_loss (loss_util.py:32-56): mean over weighted elements
-            loss = loss.mean() if weight is None else loss.sum() / (weight.sum() if weight.size(1) > 1 else weight.sum() * loss.size(1))
-        elif self.reduction == 'sum':
-            loss = loss.sum()
-        return self.loss_weight * loss
+        return _pixel_loss(_lib.LOSS_L1, pred, target, weight, self.reduction, self.loss_weight)
+
+
+@LOSS_REGISTRY.register()
+class MSELoss(nn.Module):
+    """MSE (L2) loss (basic_loss.py:55-80)."""
+
+    def __init__(self, loss_weight=1.0, reduction='mean'):
+        super().__init__()
+        _check_reduction(reduction)
+        self.loss_weight = loss_weight
+        self.reduction = reduction
+
+    def forward(self, pred, target, weight=None, **kwargs):
+        return _pixel_loss(_lib.LOSS_MSE, pred, target, weight, self.reduction, self.loss_weight)
+
+
+@LOSS_REGISTRY.register()
+class CharbonnierLoss(nn.Module):
+    """Charbonnier loss sqrt((pred - target)^2 + eps), a differentiable variant of L1
+    (basic_loss.py:83-114)."""
+
+    def __init__(self, loss_weight=1.0, reduction='mean', eps=1e-12):
+        super().__init__()
+        _check_reduction(reduction)
+        self.loss_weight = loss_weight
+        self.reduction = reduction
+        self.eps = eps
+
+    def forward(self, pred, target, weight=None, **kwargs):
+        return _pixel_loss(_lib.LOSS_CHARBONNIER, pred, target, weight, self.reduction, self.loss_weight, self.eps)
+
+
+@LOSS_REGISTRY.register()
+class WeightedTVLoss(L1Loss):
+    """Weighted total variation: the weighted L1 of the two shifted slice pairs of the prediction
+    (basic_loss.py:117-143); both operands of each pair carry a gradient."""
+
+    def __init__(self, loss_weight=1.0, reduction='mean'):
+        if reduction not in ['mean', 'sum']:
+            raise ValueError(f'Unsupported reduction mode: {reduction}. Supported ones are: mean | sum')
+        super().__init__(loss_weight=loss_weight, reduction=reduction)
+
+    def forward(self, pred, weight=None):
+        if weight is None:
+            y_weight = None
+            x_weight = None
+        else:
+            y_weight = weight[:, :, :-1, :]
+            x_weight = weight[:, :, :, :-1]
+        y_diff = super().forward(pred[:, :, :-1, :], pred[:, :, 1:, :], weight=y_weight)
+        x_diff = super().forward(pred[:, :, :, :-1], pred[:, :, :, 1:], weight=x_weight)
+        return x_diff + y_diff

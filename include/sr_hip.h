@@ -318,6 +318,28 @@ int sr_pixel_shuffle_nchw(int dtype, const void* x, int N, int C, int H, int W, 
 int sr_l1_loss(const float* pred, const float* gt, int64_t n, float weight, int mean,
                float* loss, float* grad, void* workspace, size_t ws_bytes, void* stream);
 size_t sr_l1_loss_workspace(int64_t n);
+/* Pixel-loss family (csrc/loss.hip; basicsr/losses/basic_loss.py:12-114 with weight_reduce_loss of
+ * loss_util.py:26-55) fused with its gradient.  Per element d = pred - target:
+ *   SR_LOSS_L1 |d|, SR_LOSS_MSE d^2, SR_LOSS_CHARBONNIER sqrt(d^2 + eps).
+ * pred: NCHW-contiguous [N,C,H,W] of pred_dtype (SR_F32 / SR_BF16); target: the same shape, SR_F32 or
+ * pred's dtype; weight: NULL (weight_channels 0) or an fp32 map [N,weight_channels,H,W] with 1 (broadcast
+ * over the channels) or C channels.  Pointers need only element alignment; 16-byte aligned ones are
+ * accessed with 16-byte vectors, with the same result bits.
+ *   SR_REDUCE_SUM   *loss = loss_weight * sum(w * phi)
+ *   SR_REDUCE_MEAN  the same over n = N*C*H*W without a weight, over sum(w) with a C-channel weight and
+ *                   over C * sum(w) with a one-channel weight (computed on the device)
+ *   SR_REDUCE_NONE  out[i] = loss_weight * w * phi in pred's dtype (loss is not written)
+ * grad (may be NULL), pred's dtype: loss_weight * w * phi'(d) / denom, denom as above (1 for sum and none:
+ * for 'none' the caller multiplies by the upstream gradient map).  phi' = sign(d) with sign(0) = 0, 2d,
+ * d / sqrt(d^2 + eps).  loss: fp32 device scalar.  workspace: sr_pixel_loss_workspace(n) bytes, 8-byte
+ * aligned.  Sums have a fixed order (no atomics): two runs are bit-identical; nothing synchronises or
+ * allocates, so the call can be captured in a HIP graph. */
+enum sr_loss_kind { SR_LOSS_L1 = 0, SR_LOSS_MSE = 1, SR_LOSS_CHARBONNIER = 2 };
+enum sr_loss_reduction { SR_REDUCE_NONE = 0, SR_REDUCE_MEAN = 1, SR_REDUCE_SUM = 2 };
+int sr_pixel_loss(int kind, int reduction, int pred_dtype, int target_dtype, const void* pred, const void* target,
+                  const float* weight, int weight_channels, int N, int C, int H, int W, float loss_weight, float eps,
+                  float* loss, void* out, void* grad, void* workspace, size_t ws_bytes, void* stream);
+size_t sr_pixel_loss_workspace(int64_t n);
 /* Activation backward: out = alpha * dy * (y > 0 ? 1 : neg), neg = 0 for SR_ACT_RELU, slope for
  * SR_ACT_LRELU, 1 for SR_ACT_NONE; y is the activation OUTPUT (same sign as its input). */
 int sr_act_backward(int dtype, const void* dy, const void* y, int64_t n, int act, float slope, float alpha,
