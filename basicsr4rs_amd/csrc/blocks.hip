@@ -26,19 +26,22 @@ __global__ void bilinear_up_add_kernel(const float* __restrict__ x, int N, int C
                                        const float* __restrict__ base, float* __restrict__ y) {
   const int Ho = H * s, Wo = W * s;
   const int64_t total = (int64_t)N * C * Ho * Wo;
-  const float inv = 1.f / (float)s;
+  const int s2 = 2 * s;
+  const float fs2 = (float)s2;
   for (int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (int64_t)gridDim.x * blockDim.x) {
     const int ox = (int)(o % Wo);
     const int oy = (int)((o / Wo) % Ho);
     const int64_t nc = o / ((int64_t)Wo * Ho);
-    // PyTorch area_pixel_compute_source_index, align_corners=False, scale = 1/s
-    float sy = ((float)oy + 0.5f) * inv - 0.5f;
-    float sx = ((float)ox + 0.5f) * inv - 0.5f;
-    sy = sy < 0.f ? 0.f : sy;
-    sx = sx < 0.f ? 0.f : sx;
-    const int y0 = (int)sy, x0 = (int)sx;
+    // PyTorch area_pixel_compute_source_index, align_corners=False, scale = 1/s, clamped at 0:
+    // (o + 0.5) / s - 0.5 = (2 o + 1 - s) / (2 s), split into tap and weight in integers.  Evaluated
+    // in fp32 with a rounded 1/s (s = 3) the index was off by a few 1e-7 already at 21 output columns,
+    // which moved the weights (and, next to an integer index, the taps) and the result by more than
+    // 9 u (max |tap| + |base|); for s = 1, 2, 4 that form was exact and the weights below have the
+    // same bits.
+    const int ny = max(2 * oy + 1 - s, 0), nx = max(2 * ox + 1 - s, 0);
+    const int y0 = ny / s2, x0 = nx / s2;
     const int y1 = y0 + (y0 < H - 1 ? 1 : 0), x1 = x0 + (x0 < W - 1 ? 1 : 0);
-    const float ly1 = sy - (float)y0, lx1 = sx - (float)x0;
+    const float ly1 = (float)(ny - y0 * s2) / fs2, lx1 = (float)(nx - x0 * s2) / fs2;
     const float ly0 = 1.f - ly1, lx0 = 1.f - lx1;
     const float* p = x + nc * H * W;
     const float v = ly0 * (lx0 * p[y0 * W + x0] + lx1 * p[y0 * W + x1]) +
@@ -123,11 +126,11 @@ __global__ void channel_reduce_partial(const T* __restrict__ a, int lda, int aco
 #pragma unroll
   for (int k = 0; k < 8; ++k) red[tid * 8 + k] = acc[k];
   __syncthreads();
-  if (tid < C) {
-    const int gg = tid / 8, k = tid % 8;
+  for (int c = tid; c < C; c += 256) {  // C up to 2048: more channels than threads
+    const int gg = c / 8, k = c % 8;
     float s = 0.f;
     for (int l = 0; l < lanes; ++l) s += red[(l * groups + gg) * 8 + k];
-    partial[((size_t)n * nchunk + chunk) * C + tid] = s;
+    partial[((size_t)n * nchunk + chunk) * C + c] = s;
   }
 }
 

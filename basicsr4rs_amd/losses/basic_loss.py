@@ -26,6 +26,12 @@ class _L1Fused(torch.autograd.Function):
     def forward(ctx, pred, target, loss_weight, mean):
         pred = pred.float().contiguous()
         target = target.float().contiguous()
+        # sr_l1_loss reads 16-byte vectors: a contiguous view at an odd storage offset (buf[1:1 + n]) is
+        # copied to an aligned buffer; aligned inputs, the hot path, are passed as they are
+        if pred.data_ptr() % 16:
+            pred = pred.clone()
+        if target.data_ptr() % 16:
+            target = target.clone()
         lib = _lib.load()
         n = pred.numel()
         ws_bytes = lib.sr_l1_loss_workspace(n)

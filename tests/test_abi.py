@@ -42,6 +42,20 @@ def test_invalid_arguments_raise():
     rc = lib.sr_conv3x3_fwd(d, dummy, dummy, None, None, None, None, None, None, dummy, None, None, None)
     assert rc == -1 and b'multiples of 8' in lib.sr_last_error()
     assert lib.sr_pixel_shuffle_nchw(0, dummy, 1, 3, 4, 4, 2, dummy, None) == -1  # C % r^2 != 0
+    # the 16-byte vector kernels refuse pointers that are only element-aligned (no launch)
+    odd = ctypes.c_void_p(20)
+    for dy, y, out in ((odd, dummy, dummy), (dummy, odd, dummy), (dummy, dummy, odd)):
+        assert lib.sr_act_backward(0, dy, y, 8, _lib.ACT_RELU, 0.0, 1.0, out, None) == -1
+        assert b'act_backward: tensors must be 16-byte aligned' in lib.sr_last_error()
+    for x, out in ((odd, dummy), (dummy, odd)):
+        assert lib.sr_row_scale(0, x, 4, 8, 2, dummy, out, None) == -1
+        assert b'row_scale: tensors must be 16-byte aligned' in lib.sr_last_error()
+    for x, u, s, t, out in ((None, odd, dummy, None, dummy), (None, dummy, dummy, None, odd), (odd, dummy, dummy, None, dummy),
+                            (None, dummy, odd, None, dummy), (None, dummy, dummy, odd, dummy)):
+        assert lib.sr_nc_affine(0, x, u, s, t, 1, 4, 8, 1.0, 0.1, 0.0, out, None) == -1
+        assert b'nc_affine: bad arguments' in lib.sr_last_error()
+    assert lib.sr_channel_reduce(0, dummy, 12, 0, None, 0, 0, 1, 4, 12, 1.0, dummy, dummy, 1 << 20, None) == -1
+    assert b'channel_reduce: bad arguments (C multiple of 8' in lib.sr_last_error()
 
 
 def test_dcn_fused_forward_query_and_validation():

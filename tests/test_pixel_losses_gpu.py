@@ -12,6 +12,11 @@ Bounds (from the issue, not from the kernel's results): loss |got - ref| <= 1e-5
 gradient |got - ref| <= 1e-5 * |ref| + 1e-6 * max|ref| elementwise; bf16 gradient one bf16 rounding,
 2^-8 relative; exact zeros at d == 0 and under zero weight; the target gradient, an element-aligned
 (storage-offset) prediction and a second call are bitwise equal to their counterparts.
+
+The unweighted L1 mean / sum whose target needs no gradient -- the loss of every SR train YAML -- runs
+another kernel, sr_l1_loss (csrc/eltwise.hip): the test_l1_fused_* tests put it under the same reference
+and bounds, assert the autograd node so that they cannot run sr_pixel_loss instead, and cover a NaN
+prediction and storage-offset views of both operands.
 """
 import functools
 
@@ -102,12 +107,16 @@ def _build(kind, reduction, lw=LW):
     return build_loss(opt)
 
 
-def _run(kind, reduction, pred, target, weight, up=None, target_grad=True):
-    """(loss, pred gradient, target gradient) of the HIP path.  The target asks for its gradient, which
-    also takes the unweighted L1 mean / sum onto sr_pixel_loss (sr_l1_loss has no target gradient)."""
+def _run(kind, reduction, pred, target, weight, up=None, target_grad=True, names=None):
+    """(loss, pred gradient, target gradient) of the HIP path.  By default the target asks for its
+    gradient, which also takes the unweighted L1 mean / sum onto sr_pixel_loss (sr_l1_loss has no target
+    gradient); with target_grad=False that case runs sr_l1_loss.  ``names``: a list that receives the
+    name of the loss's autograd node."""
     p = pred.detach().requires_grad_(True)
     t = target.detach().requires_grad_(target_grad)
     loss = _build(kind, reduction)(p, t, weight)
+    if names is not None:
+        names.append(type(loss.grad_fn).__name__)
     (loss * up).sum().backward() if reduction == 'none' else loss.backward()
     return loss.detach(), p.grad, t.grad
 
@@ -213,6 +222,68 @@ def test_storage_offset_view_bitwise(cuda, kind, wmode, reduction, shape):
     b = _run(kind, reduction, pv, dev['target'], wv, dev['up'])
     for x, y in zip(a, b):
         assert torch.equal(x, y)
+
+
+@pytest.mark.parametrize('shape', list(SHAPES))
+@pytest.mark.parametrize('reduction', ['mean', 'sum'])
+def test_l1_fused_path_matches_float64(cuda, reduction, shape):
+    """The hot path of every SR train YAML: unweighted L1 mean / sum with a target that needs no
+    gradient runs sr_l1_loss (csrc/eltwise.hip), not sr_pixel_loss; same reference, same bounds."""
+    shp = SHAPES[shape]()
+    host, dev = _inputs(shp)
+    ref_loss, ref_grad = _ref('L1Loss', host['pred'], host['target'], None, reduction)
+    names = []
+    loss, gp, gt = _run('L1Loss', reduction, dev['pred'], dev['target'], None, target_grad=False, names=names)
+    assert '_L1Fused' in names[0], names
+    what = f'L1Loss fused {reduction} {shp}'
+    assert gt is None and loss.dtype == torch.float32 and gp.dtype == torch.float32 and loss.shape == ()
+    _check_loss(loss, ref_loss, what)
+    _check_grad(gp, ref_grad, what)
+    zero = host['pred'] == host['target']
+    assert zero.any() or shape == 'tail'
+    assert (gp.cpu()[zero] == 0).all()
+
+
+@pytest.mark.parametrize('reduction', ['mean', 'sum'])
+def test_l1_fused_nan_prediction_gives_nan_loss(cuda, reduction):
+    """SRRSModel skips the step on a non-finite loss: one NaN in the prediction must reach the loss."""
+    shp = SHAPES['odd']()
+    _, dev = _inputs(shp)
+    pred = dev['pred'].clone()
+    pred[1, 2, 3, 4] = float('nan')
+    names = []
+    loss, gp, _ = _run('L1Loss', reduction, pred, dev['target'], None, target_grad=False, names=names)
+    assert '_L1Fused' in names[0], names
+    assert torch.isnan(loss).item()
+    ok = torch.ones(shp, dtype=torch.bool)
+    ok[1, 2, 3, 4] = False
+    assert torch.isfinite(gp.cpu()[ok]).all()
+
+
+def _offset_view(x, off):
+    buf = torch.empty(x.numel() + 8, device=x.device, dtype=x.dtype)
+    v = buf[off:off + x.numel()].view(x.shape)
+    v.copy_(x)
+    assert v.is_contiguous() and v.data_ptr() % 16 == (4 * off) % 16 and torch.equal(v, x)
+    return v
+
+
+@pytest.mark.parametrize('shape,which,off', [('odd', w, o) for w in ('pred', 'target', 'both') for o in (1, 2, 3)] +
+                         [('tail', 'both', 1), ('big', 'both', 3)])
+@pytest.mark.parametrize('reduction', ['mean', 'sum'])
+def test_l1_fused_storage_offset_view(cuda, reduction, shape, which, off):
+    """Contiguous views at element offsets 1, 2, 3 of a larger buffer (4, 8, 12 bytes past a 16-byte
+    boundary), e.g. buf[1:1 + n].view(shape), give the bits of aligned clones on the sr_l1_loss path."""
+    shp = SHAPES[shape]()
+    _, dev = _inputs(shp)
+    assert dev['pred'].data_ptr() % 16 == 0 and dev['target'].data_ptr() % 16 == 0
+    pv = _offset_view(dev['pred'], off) if which in ('pred', 'both') else dev['pred']
+    tv = _offset_view(dev['target'], off) if which in ('target', 'both') else dev['target']
+    names = []
+    a = _run('L1Loss', reduction, dev['pred'], dev['target'], None, target_grad=False, names=names)
+    b = _run('L1Loss', reduction, pv, tv, None, target_grad=False, names=names)
+    assert all('_L1Fused' in n for n in names), names
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
 
 
 def _tv_ref(pred, weight, reduction, lw=LW):
