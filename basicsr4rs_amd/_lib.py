@@ -118,6 +118,8 @@ SIGNATURES = {
     'sr_bicubic_up_hp': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     'sr_val_metrics_workspace': (_sz, [_i, _i, _i, _i, _i]),
     'sr_val_metrics': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'sr_niqe_moments_workspace': (_sz, [_i, _i, _i, _i, _i, _i]),
+    'sr_niqe_moments': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'sr_nchw_to_nhwc': (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'sr_nhwc_to_nchw': (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'sr_pixel_shuffle_nchw': (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -41,13 +41,6 @@ struct VmArgs {
   unsigned long long* part_sse;  // [N*C][tiles]
 };
 
-SR_DEV unsigned char quantise(float v) {
-  v = fminf(fmaxf(v, -1.f), 1.f);
-  float t = __fmul_rn(__fadd_rn(v, 1.f), 0.5f);
-  t = rintf(__fmul_rn(t, 255.f));
-  return (unsigned char)fminf(fmaxf(t, 0.f), 255.f);
-}
-
 __global__ __launch_bounds__(VM_THREADS) void val_metrics_kernel(VmArgs a) {
   __shared__ unsigned char pa[VM_P * VM_P], pb[VM_P * VM_P];
   __shared__ double V[5][VM_T][VM_P];  // the five moments filtered down the rows

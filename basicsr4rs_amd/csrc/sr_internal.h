@@ -30,5 +30,15 @@ enum SrKnob {
   K_COUNT
 };
 int sr_knob(SrKnob k);
+
+// [-1, 1] fp32 -> ubyte exactly as utils/img_util.py:minusone_one_tensor_to_ubyte_numpy: clamp,
+// (t + 1) * 0.5, * 255 with individually rounded fp32 operations, round half to even, clip.  Shared by
+// the validation-metric kernels (metrics.hip, niqe.hip) so that both see the host's pixel values.
+__device__ __forceinline__ unsigned char quantise(float v) {
+  v = fminf(fmaxf(v, -1.f), 1.f);
+  float t = __fmul_rn(__fadd_rn(v, 1.f), 0.5f);
+  t = rintf(__fmul_rn(t, 255.f));
+  return (unsigned char)fminf(fmaxf(t, 0.f), 255.f);
+}
 // diagnostics buffer of per-block clock stamps (sr_conv3x3_set_stamps; null = off)
 extern unsigned long long* g_sr_stamps;

@@ -2,11 +2,13 @@
 from copy import deepcopy
 
 from ..utils.registry import METRIC_REGISTRY
+from .niqe import calculate_niqe, calculate_niqe_band, calculate_niqe_none, calculate_rs_niqe
 from .psnr_ssim import (calculate_psnr, calculate_psnr_band, calculate_psnr_pt, calculate_ssim, calculate_ssim_band,
                         calculate_ssim_pt)
 
 __all__ = ['calculate_psnr', 'calculate_psnr_band', 'calculate_psnr_pt', 'calculate_ssim', 'calculate_ssim_band',
-           'calculate_ssim_pt', 'calculate_metric']
+           'calculate_ssim_pt', 'calculate_niqe', 'calculate_rs_niqe', 'calculate_niqe_band', 'calculate_niqe_none',
+           'calculate_metric']
 
 
 def calculate_metric(data, opt):

@@ -14,7 +14,8 @@ saved visuals are split into RGB (channels 0-2) and NIR (channel 3) PNGs (srrs_m
 
 ``val.device_metrics: true`` (default false) takes the PSNR / SSIM scores from the ``sr_val_metrics``
 HIP kernel on the device tensors instead (ops/metrics.py): the same table, PSNR exactly and SSIM to
-1e-10, without bringing the images to the host unless they are saved.
+1e-10, without bringing the images to the host unless they are saved.  NIQE entries take their block
+moments from ``sr_niqe_moments`` on the same path (the fits and the score on the host, metrics/niqe.py).
 """
 import os
 from collections import OrderedDict
@@ -25,7 +26,7 @@ import torch
 
 from ..metrics import calculate_metric
 from ..ops.conv import async_wgrad
-from ..ops.metrics import DEVICE_METRICS, scores_from_device
+from ..ops.metrics import DEVICE_METRICS, NIQE_DEVICE_METRICS, niqe_device_reason, scores_from_device
 from ..utils.img_util import imwrite, minusone_one_tensor_to_ubyte_numpy
 from ..utils.logger import get_root_logger
 from ..utils.registry import MODEL_REGISTRY
@@ -159,11 +160,16 @@ class SRRSModel(SRModel):
         """Whether this image's scores can come from ``sr_val_metrics`` (val.device_metrics).  The
         kernel stands in for calculate_psnr / calculate_ssim and their ``_band`` forms without the Y
         channel, on one image of at least two channels (the host conversion repeats a single channel
-        to three, utils/img_util.py:make_grid); anything else takes the host path whole, with one
+        to three, utils/img_util.py:make_grid); ``sr_niqe_moments`` stands in for calculate_niqe /
+        calculate_rs_niqe with ``convert_to: y`` on one or three bands and for calculate_niqe_band, on
+        images of at least 96 x 96 after the crop; anything else takes the host path whole, with one
         warning per reason."""
         reason = None
+        niqe = []
         for name, o in self.opt['val']['metrics'].items():
-            if o.get('type') not in DEVICE_METRICS:
+            if o.get('type') in NIQE_DEVICE_METRICS:
+                niqe.append((name, o))  # judged below, once the image shape is known to be usable
+            elif o.get('type') not in DEVICE_METRICS:
                 reason = f'metric {name!r} is {o.get("type")}'
             elif o.get('test_y_channel', False):
                 reason = f'metric {name!r} sets test_y_channel'
@@ -178,6 +184,13 @@ class SRRSModel(SRModel):
                 reason = f'the validation batch is {self.output.shape[0]}, not 1'
             elif self.output.shape[1] < 2:
                 reason = 'the images have one channel'
+        if reason is None:
+            # NIQE from sr_niqe_moments: the Y of three bands or one band, at least one 96 x 96 block
+            for name, o in niqe:
+                why = niqe_device_reason(o, *self.output.shape[1:])
+                if why:
+                    reason = f'metric {name!r} ({o.get("type")}): {why}'
+                    break
         if reason is None:
             return True
         warned = self.__dict__.setdefault('_device_metrics_warned', set())

@@ -299,6 +299,31 @@ int sr_val_metrics(const float* sr, const float* gt, int N, int C, int H, int W,
                    void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * NIQE block moments (csrc/niqe.hip): the device form of metrics/niqe.py:niqe_plane + niqe_moments for P
+ * planes (1 <= P <= 64) of x, fp32 NCHW [N,C,H,W] in nominal [-1, 1], in one call.  The host turns the
+ * moments into scores (metrics/niqe.py:niqe_from_moments).
+ *   plane_desc  host int [P][4]: image n, then channels c0, c1, c2.  c1 = c2 = -1: the plane is band c0 as
+ *               it is; otherwise the BT.601 Y of the three, y_coef[0]*c0 + y_coef[1]*c1 + y_coef[2]*c2 +
+ *               y_coef[3] on the [0, 1] pixels (y_coef: host double [4]; NULL allowed without such a plane).
+ *   window      host double [49], the 7 x 7 window as scipy.ndimage.convolve takes it (row-major).
+ * Pixels are quantised to ubyte like sr_val_metrics, `crop` pixels dropped on each edge, the Y rounded, and
+ * the plane truncated (top-left) to Hb x Wb = whole 96 x 96 blocks, bh x bw of them: the host plane exactly.
+ *   moments     device double [P][2][bh][bw][5][6]: per scale (96-blocks of the plane, 48-blocks of its
+ *               antialiased half-size resample), block and map (the MSCN block, its products with its
+ *               circular rolls by (0,1), (1,0), (1,1), (1,-1)): count and sum of squares of the negative
+ *               elements, the same of the positive ones, sum |x|, sum x^2.
+ *   planes_out  optional device fp32 [P][Hb][Wb], the planes; mscn_out: optional, the scale-1 MSCN maps.
+ * Workspace of sr_niqe_moments_workspace(...) bytes (4-byte aligned; 0 = unsupported shape).  Fixed-order
+ * reductions, no atomics: two calls give identical bytes.  SR_EINVAL for null pointers, non-positive sizes,
+ * crop < 0, H or W after the crop below 96, P outside 1..64, an image or channel index out of range, or a
+ * workspace that is too small; SR_ETOOBIG when P * Hb * Wb exceeds 2^31 - 1.  Nothing is launched then.
+ * ------------------------------------------------------------------------------- */
+size_t sr_niqe_moments_workspace(int N, int C, int H, int W, int crop, int P);
+int sr_niqe_moments(const float* x, int N, int C, int H, int W, int crop, int P, const int* plane_desc,
+                    const double* y_coef, const double* window, double* moments, float* planes_out, float* mscn_out,
+                    void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Layout / elementwise ops (HBM-bound).
  * ------------------------------------------------------------------------------- */
 /* NCHW fp32 [N,C,H,W] -> NHWC dtype [N,H,W,Cp] (channels >= C zero):
