@@ -312,7 +312,7 @@ def swin_mask(h, w, ws, s):
         for wsl in (slice(0, -ws), slice(-ws, -s), slice(-s, None)):
             img[:, hs, wsl, :] = cnt
             cnt += 1
-    mw = window_partition(img, ws).view(-1, ws * ws)
+    mw = window_partition(img, ws).reshape(-1, ws * ws)  # (a view of a one-window-row map is not contiguous)
     m = mw.unsqueeze(1) - mw.unsqueeze(2)
     return m.masked_fill(m != 0, -100.0).masked_fill(m == 0, 0.0)
 

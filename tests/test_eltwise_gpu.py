@@ -16,15 +16,12 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from tests._fp64 import U, _assert_outside_unchanged, _bf16_ulp, _bits, _check, _ids, _rne_bf16  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
-U = 2.0**-24
 DTYPES = [torch.float32, torch.bfloat16]
 SWEEP = 8192 * 256  # vectors one sweep of the element-wise kernels' grid covers
-
-
-def _ids(dt):
-    return 'f32' if dt == torch.float32 else 'bf16'
 
 
 def _lib():
@@ -40,47 +37,6 @@ def _randn(shape, dtype, seed, scale=1.0):
 def _f32(x):
     """A Python float rounded to fp32, as a float64 value (what a kernel receives as a float argument)."""
     return float(np.float32(x))
-
-
-def _rne_bf16(x64):
-    """One round-to-nearest-even of float64 values to 8 significant bits (bf16; values in normal range)."""
-    m, e = np.frexp(x64.numpy())
-    return torch.from_numpy(np.ldexp(np.rint(m * 256.0) / 256.0, e))
-
-
-def _bf16_ulp(x64):
-    _, e = np.frexp(x64.abs().clamp(min=2.0**-120).numpy())
-    return torch.from_numpy(np.ldexp(np.ones_like(e, dtype=np.float64), e - 8))
-
-
-def _check(got, ref, fbound, what):
-    """got (device, fp32 or bf16) against the float64 ref; fbound: the derived fp32 bound (tensor or 0)."""
-    got64 = got.detach().double().cpu()
-    assert got64.shape == ref.shape, (what, got64.shape, ref.shape)
-    fb = fbound if torch.is_tensor(fbound) else torch.full_like(ref, float(fbound))
-    if got.dtype == torch.float32:
-        target, bound = (ref.float().double(), fb) if not fb.any() else (ref, fb)
-    else:
-        target = _rne_bf16(ref)
-        bound = torch.where(fb > 0, _bf16_ulp(torch.maximum(target.abs(), got64.abs())) + fb, fb)
-    err = (got64 - target).abs()
-    assert torch.isfinite(got64).all(), what
-    ratio = torch.where(err > 0, err / bound.clamp(min=1e-300), torch.zeros_like(err))
-    rounded = got.dtype != torch.float32 or not fb.any()
-    print(f'{what} [{_ids(got.dtype)}]: max|err| {err.max().item():.3e}, bound there '
-          f'{bound.reshape(-1)[err.argmax()].item():.3e}, max err/bound {ratio.max().item():.3f}' +
-          (f', {(err > 0).double().mean().item():.2%} of elements differ from the rounded reference' if rounded else ''))
-    assert (err <= bound).all(), (what, err.max().item())
-
-
-def _bits(t):
-    return t.view(torch.int32 if t.element_size() == 4 else torch.int16)
-
-
-def _assert_outside_unchanged(buf, before, coff, C, what):
-    keep = torch.ones(buf.shape[-1], dtype=torch.bool, device=buf.device)
-    keep[coff:coff + C] = False
-    assert torch.equal(_bits(buf)[..., keep], _bits(before)[..., keep]), f'{what}: wrote outside the channel slice'
 
 
 SENTINEL = -12345.0
@@ -487,6 +443,9 @@ def test_bilinear_up_add_gradients(cuda):
 
 # ---------------------------------------------------------------------- add_pos_embed, pos_embed_grad
 
+APE_BIG = (2, 96, 96, 240, 240)  # N P Cp and P C both past one sweep of 8192 blocks x 256 threads
+
+
 class _Ape(nn.Module):
 
     def __init__(self, P, c):
@@ -497,7 +456,7 @@ class _Ape(nn.Module):
 
 
 @pytest.mark.parametrize('dtype', DTYPES, ids=_ids)
-@pytest.mark.parametrize('shape', [(3, 4, 6, 60, 64), (2, 8, 8, 184, 184)], ids=str)
+@pytest.mark.parametrize('shape', [(3, 4, 6, 60, 64), (2, 8, 8, 184, 184), APE_BIG], ids=str)
 def test_add_pos_embed_and_grad(cuda, shape, dtype):
     """y = x + pos on the first C of Cp channels (one fp32 sum: u |ref|), padded channels copied through
     bitwise; dx = dy bitwise; dpos = sum over the batch of dy (N terms from 0: (N - 1) u sum|dy|), either
@@ -507,6 +466,8 @@ def test_add_pos_embed_and_grad(cuda, shape, dtype):
     from basicsr4rs_amd.utils.flat import FlatParams
     N, H, W, c, cp = shape
     P = H * W
+    if shape == APE_BIG:
+        assert SWEEP < P * c < N * P * cp < 3 * SWEEP  # both kernels' grid-stride loops run again
     x, dy = _randn((N, H, W, cp), dtype, 96), _randn((N, H, W, cp), dtype, 97)
     dsum = dy.double()[..., :c].reshape(N, P, c).sum(0, keepdim=True)
     dmag = dy.double()[..., :c].reshape(N, P, c).abs().sum(0, keepdim=True)

@@ -82,6 +82,117 @@ def test_window_attention_fwd_bwd(cuda, shift, dtype, geom):
     assert (dtab.double().cpu() - td.grad).abs().max().item() < tol * max(1.0, td.grad.abs().max().item())
 
 
+ATT_UPW = 4  # windows per wave of the MFMA backward (csrc/swin.hip)
+SR_EINVAL = -1
+
+
+def _attn_vs_oracle(cuda, dtype, geom, shift, mfma):
+    """Forward and backward at (b, h, w, nH, hd, ws, hdp) against the float64 oracle with the tolerances of
+    test_window_attention_fwd_bwd; the padded head columns of out and dqkv are exactly 0; ``mfma``: which
+    kernels sr_window_attn_bwd_parts reports (slot rows < 0: MFMA; units > 0: fp32-FMA)."""
+    from basicsr4rs_amd import _lib
+    b, h, w, nH, hd, ws, hdp = geom
+    torch.manual_seed(11 + shift)
+    C = nH * hd
+    scale = hd**-0.5
+    qkv = torch.randn(b, h, w, 3 * C).to(dtype)
+    table = torch.randn((2 * ws - 1)**2, nH) * 0.5
+    dout = torch.randn(b, h, w, C).to(dtype)
+    qd = qkv.double().requires_grad_()
+    td = table.double().requires_grad_()
+    ref = O.window_attention_core(qd, nH, ws, shift, scale, td)
+    ref.backward(dout.double())
+    g = S.AttnGeom(C, nH, ws, shift, hdp)
+    assert g.hd == hd
+    parts = _lib.load().sr_window_attn_bwd_parts(_lib.dtype_code(dtype), b, h, w, ws, nH, hd, hdp, 3 * nH * hdp, nH * hdp)
+    units = b * (h // ws) * (w // ws)
+    assert parts == (-nH * ((units + ATT_UPW - 1) // ATT_UPW) if mfma else units * nH)
+    qp = _qkv_padded(qkv, nH, hd, hdp).to(cuda).contiguous()
+    out, lse = S.window_attn(qp, g, b, h, w, scale, table.to(cuda))
+    got = out.view(b, h, w, nH, hdp)[..., :hd].reshape(b, h, w, C).double().cpu()
+    tol = 2e-2 if dtype == torch.bfloat16 else 1e-4
+    what = f'window attention {geom} shift {shift} {dtype}'
+    errs = [(got - ref.detach()).abs().max().item() / max(1.0, ref.abs().max().item())]
+    assert (out.view(b, h, w, nH, hdp)[..., hd:] == 0).all(), what
+    assert torch.isfinite(lse).all(), what
+    dop = F.pad(dout.view(b, h, w, nH, hd), (0, hdp - hd)).reshape(b, h, w, nH * hdp).to(cuda).contiguous()
+    dqkv, dtab = S.window_attn_bwd(qp, out, dop, lse, g, b, h, w, scale, table.to(cuda))
+    dq = dqkv.view(b, h, w, 3, nH, hdp)[..., :hd].reshape(b, h, w, 3 * C).double().cpu()
+    assert (dqkv.view(b, h, w, 3, nH, hdp)[..., hd:] == 0).all(), what
+    errs.append((dq - qd.grad).abs().max().item() / max(1.0, qd.grad.abs().max().item()))
+    errs.append((dtab.double().cpu() - td.grad).abs().max().item() / max(1.0, td.grad.abs().max().item()))
+    print(f'{what}: out / dqkv / dbias_table max|err| over max(1, max|ref|) = '
+          f'{errs[0]:.3e} / {errs[1]:.3e} / {errs[2]:.3e}, tolerance {tol:g}')
+    assert max(errs) < tol, (what, errs)
+
+
+MFMA_GEOM = [
+    # b, h, w, nH, hd, ws, hdp, shifts
+    ((1, 24, 40, 3, 30, 8, 32), (1, 3, 7)),  # H != W; 15 windows: the last backward wave holds 3
+    ((2, 8, 24, 2, 16, 8, 32), (3, )),  # a single window row: every window wraps vertically
+    ((1, 24, 8, 2, 16, 8, 32), (3, )),  # a single window column
+]
+
+
+@pytest.mark.parametrize('geom,shift', [(g, s) for g, ss in MFMA_GEOM for s in ss], ids=str)
+def test_window_attention_mfma_shift_geometry(cuda, geom, shift):
+    """The MFMA kernels (bf16, window 8, heads padded to 32) at shifts other than 0 and ws / 2: region()
+    boundaries at L - ws and L - s and the gather wrap of token_pixel for odd shifts, on maps with
+    H != W, with one window row or column (whose only window holds all three regions of that axis), and
+    with a window count that is no multiple of the windows per backward wave."""
+    assert (geom[0] * (geom[1] // 8) * (geom[2] // 8)) % ATT_UPW or min(geom[1], geom[2]) == 8
+    _attn_vs_oracle(cuda, torch.bfloat16, geom, shift, mfma=True)
+
+
+FALLBACK_GEOM = [
+    # b, h, w, nH, hd, ws, hdp, shifts, dtypes
+    ((2, 14, 21, 2, 12, 7, 16), (0, 3, 6), (torch.float32, torch.bfloat16)),  # T = 49: 15 idle lanes per wave
+    ((1, 10, 15, 3, 10, 5, 16), (2, ), (torch.float32, torch.bfloat16)),
+    ((1, 16, 24, 2, 16, 8, 32), (5, ), (torch.float32, )),  # window 8 in fp32 (bf16 takes the MFMA kernels)
+    ((1, 8, 12, 2, 32, 4, 32), (1, ), (torch.float32, torch.bfloat16)),  # hd == hdp == DMAX
+    ((1, 8, 12, 3, 4, 4, 8), (3, ), (torch.float32, torch.bfloat16)),  # hd < 8
+]
+
+
+@pytest.mark.parametrize('geom,shift,dtype', [(g, s, d) for g, ss, ds in FALLBACK_GEOM for s in ss for d in ds], ids=str)
+def test_window_attention_fallback_geometry(cuda, geom, shift, dtype):
+    """wattn_fwd_kernel / wattn_bwd_kernel (fp32 FMA, one lane per query token) at the windows, shifts
+    and head widths no other test runs: window 7 (the SwinIR JPEG configurations) and 5, window 8 in
+    fp32, a full 32-wide head and a 4-wide one."""
+    _attn_vs_oracle(cuda, dtype, geom, shift, mfma=False)
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize('bad', ['shift == ws', 'ws == 9', 'hd > hdp'])
+def test_window_attention_refusals(cuda, bad, dtype):
+    """Geometry outside attn_setup's envelope returns SR_EINVAL from the forward and the backward and
+    launches nothing: every output keeps its sentinel bits."""
+    from basicsr4rs_amd import _lib
+    lib = _lib.load()
+    b, h, w, nH, hd, ws, hdp, shift = {'shift == ws': (1, 16, 16, 2, 16, 8, 32, 8), 'ws == 9': (1, 18, 18, 2, 16, 9, 32, 4),
+                                       'hd > hdp': (1, 16, 16, 2, 16, 8, 8, 4)}[bad]
+    ldq, ldo = 3 * nH * max(hd, hdp), nH * max(hd, hdp)
+    qkv = torch.randn(b, h, w, ldq, device=cuda).to(dtype)
+    table = torch.randn((2 * ws - 1)**2, nH, device=cuda)
+    units = b * (h // ws) * (w // ws) * nH
+    fill = lambda *s, dt=dtype: torch.full(s, -1024.0, device=cuda, dtype=dt)
+    out, lse = fill(b, h, w, ldo), fill(units * ws * ws, dt=torch.float32)
+    code = _lib.dtype_code(dtype)
+    rc = lib.sr_window_attn_fwd(code, _lib.ptr(qkv), ldq, b, h, w, ws, shift, nH, hd, hdp, 0.25, _lib.ptr(table),
+                                _lib.ptr(out), ldo, _lib.ptr(lse), _lib.stream())
+    assert rc == SR_EINVAL
+    dqkv, dtab = fill(b, h, w, ldq), fill((2 * ws - 1)**2, nH, dt=torch.float32)
+    wsb = max(lib.sr_window_attn_bwd_workspace(b, h, w, ws, nH), 4096)
+    wsp = fill(wsb // 4, dt=torch.float32)
+    rc = lib.sr_window_attn_bwd(code, _lib.ptr(qkv), ldq, _lib.ptr(out), _lib.ptr(out), ldo, _lib.ptr(lse), b, h, w, ws,
+                                shift, nH, hd, hdp, 0.25, _lib.ptr(table), _lib.ptr(dqkv), _lib.ptr(dtab), _lib.ptr(wsp),
+                                wsb, 0, _lib.stream())
+    assert rc == SR_EINVAL
+    torch.cuda.synchronize()
+    for t in (out, lse, dqkv, dtab, wsp):
+        assert (t == -1024.0).all()
+
+
 @pytest.mark.parametrize('shift', [0, 4])
 @pytest.mark.parametrize('geom', [(2, 16, 24, 6, 30), (3, 8, 40, 3, 32), (1, 24, 24, 2, 16), (32, 8, 8, 6, 30)])
 def test_window_attention_bwd_reduce_paths_bitwise(cuda, shift, geom):
