@@ -15,306 +15,22 @@
 // same 16-byte chunk image.  The epilogue stages the fp32 tile through LDS and applies
 // bias, activation, ReLU-mask gate, scale, residual, pixel-shuffle / NCHW store with
 // 16-byte coalesced stores.
-#include <atomic>
-#include <cstdlib>
+//
+// This file has the host side -- the kernel selection (every fwd_use_* / wg_use_* predicate, fwd_kind), the split
+// plans and the sr_conv3x3_* entry points -- and, first, the kernels that have no file of their own yet.  Every
+// launch is a function next to its kernels; conv3x3_args.h declares them and the predicates they call.
+//   conv3x3_args.h        FwdArgs / WgArgs, epilogue bits, FwdKind, launcher and predicate declarations
+//   conv3x3_dev.h         device helpers of more than one family (epilogue_tile, mfma_chunk, swz128, ...)
+//   conv3x3_fwd_band.hip  conv3x3_fwd_band_kernel
+//   conv3x3_linear.hip    linear_wk_kernel, conv3x3_lin_kernel, linear_wgrad_kernel
 #include <utility>
 #include <type_traits>
-#include "sr_common.h"
-#include "sr_internal.h"
+#include "conv3x3_args.h"
+#include "conv3x3_dev.h"
+
+using namespace sr_conv;
 
 namespace {
-
-// set by sr_conv3x3_set_variant (tests / A-B timing): an sr_conv_variant of include/sr_hip.h
-int g_variant = SR_VARIANT_AUTO;
-bool variant_is(int v) { return g_variant == v; }
-// SR_VARIANT_TILE_ONLY: never a 256x256 kernel (nor any of the narrow-conv families)
-bool tile_only() { return variant_is(SR_VARIANT_TILE_ONLY); }
-
-// Bits of the compile-time epilogue code E of the band, lin and linear_wk kernels (a template argument, so
-// the values are part of the kernel names): bits 0-1 act, 2-3 gate (0 none, 1 pre-residual (g > 0 ? 1 :
-// gate_slope), 2 pre-residual GELU'(g), 3 post-residual mask on columns gcol0..gcol1), then one bit per operand.
-// Bit 7 is the channel sums in the band kernel and the per-image row scale in the lin kernels.
-enum : int { EPI_ACT = 3, EPI_GATE_SHIFT = 2, EPI_GATE = 3, EPI_RES = 16, EPI_RES2 = 32, EPI_AUX = 64 };
-enum : int { BAND_CS = 128, BAND_RSC = 256, BAND_DOT = 512, BAND_STRIP = 1024 };
-enum : int { LIN_RSC = 128 };
-
-struct FwdArgs {
-  const void* x;
-  const void* w;
-  const float* bias;
-  const void* gate;
-  const void* res;
-  const float* aff_scale;
-  const float* aff_shift;
-  void* y;
-  uint32_t x_bytes, w_bytes, g_bytes, r_bytes;
-  int N, H, W, M;
-  int Cin, ldx, xcoff, in_ps, cpt;  // cpt: 16-byte chunks per tap
-  int Cout, Cout_real, ldw, nkc;    // nkc: total K chunks (9*cpt)
-  int ldy, ycoff, out_ps, out_nchw;
-  int act;
-  float slope, alpha;
-  int ldg, gcoff;
-  float gate_slope;
-  int ldr, rcoff;
-  float beta;
-  const void* res2;
-  uint32_t r2_bytes;
-  int ldr2, r2coff, rcols;
-  float beta2;
-  int in_up;  // nearest-neighbour upsample factor folded into the A gather (1 = none)
-  int tap0;   // 4 for 1x1 (linear) convs: the single tap is the centre one
-  int gate_mode;  // 0: v *= (gate > 0 ? 1 : gate_slope); 1: v *= GELU'(gate); 2: post-residual, gcol0..gcol1
-  int gcol0, gcol1;
-  void* aux;      // optional store of the pre-activation value (same layout as y)
-  float* colsum;  // optional per-(wave, row chunk) column sums of the stored y (see epilogue_tile)
-  int tiles_n, tiles;
-  FastDiv fd_cpt, fd_W, fd_H, fd_cps;  // fd_cps: divide by C' (channels per shuffle slot)
-  FastDiv fd_r;                        // divide by in_ps (1 when none)
-  unsigned long long* stamps;  // diagnostics: per-row clock stamps of the band kernel (null = off)
-  const float* row_scale;  // optional per-image factor on alpha (SwinIR stochastic depth)
-  FastDiv fd_hw;           // divide by H*W (pixel -> image)
-  // LayerNorm of the input rows fused into the lin kernel's prologue (sr_linear_ln_fwd)
-  const float* ln_g;
-  const float* ln_b;
-  void* ln_out;  // the normalised rows [M][Cin] (bf16), for the weight gradient and backward
-  float* ln_mean;
-  float* ln_rstd;
-  int ln_C;      // channels normalised (the rest of the Cin padded columns are written as zeros)
-  float ln_eps;
-  const void* dot;  // band kernel, with colsum: partial sums of y * dot (sr_conv3x3_desc.dot)
-  uint32_t d_bytes;
-  int ldd, dcoff;
-  int cs_band;  // band kernel: colsum / dot partial rows summed over the band's rows (band_cs_rows), 0: per row
-  int strip64;  // pph kernel over 64-px column strips of a wider image: 256-row tiles are 4 rows x 64 px
-};
-
-// alpha of output row m: a.alpha, times the per-image row_scale when given
-SR_DEV float row_alpha(const FwdArgs& a, int m) {
-  return a.row_scale ? a.alpha * a.row_scale[fdiv((uint32_t)m, a.fd_hw)] : a.alpha;
-}
-
-template <typename T>
-SR_DEV void mfma_chunk(const u32x4& a, const u32x4& b, f32x4& acc);
-
-template <>
-SR_DEV void mfma_chunk<bf16_t>(const u32x4& a, const u32x4& b, f32x4& acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(s16x8, a),
-                                                __builtin_bit_cast(s16x8, b), acc, 0, 0, 0);
-}
-template <>
-SR_DEV void mfma_chunk<float>(const u32x4& a, const u32x4& b, f32x4& acc) {
-  // one 16-byte chunk = 4 consecutive K elements per lane: 4 f32 MFMAs (K=4 each); the
-  // lane->k assignment is the same for A and B so the permuted K order sums correctly.
-#pragma unroll
-  for (int s = 0; s < 4; ++s)
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[s]), __uint_as_float(b[s]), acc,
-                                               0, 0, 0);
-}
-
-// Byte offset of chunk c of row r inside a [rows][128 B] swizzled image.
-SR_DEV uint32_t swz128(uint32_t r, uint32_t c) { return r * 128u + ((c ^ (r & 7u)) << 4); }
-
-// Fused epilogue over a [ROWS][BN] fp32 tile staged in LDS (row stride CSTR floats):
-// bias, activation, gate, alpha, residual, then a plain / pixel-shuffled NHWC store of
-// 8-channel (16-byte bf16 / 32-byte f32) groups, or the fp32 NCHW affine store.
-template <typename T, int ROWS, int BN, int NT>
-SR_DEV void epilogue_tile(const FwdArgs& a, const float* Cs, int CSTR, int m0, int n0, int tid) {
-  constexpr int SZ = Elt<T>::SIZE;
-  // tile row -> NHWC pixel: m0 + row, or (a.strip64: the pph kernel's column strips, tiles ordered
-  // (image, strip, 4-row block)) row r of the 256-row tile is pixel (r / 64, r % 64) of its block
-  int sbase = 0;
-  if (a.strip64) {
-    const int tm = m0 >> 8, tps = a.H >> 2, ns = a.W >> 6;
-    const int img = tm / (tps * ns), rem = tm - img * tps * ns, j = rem / tps, yb = rem - j * tps;
-    sbase = (img * a.H + yb * 4) * a.W + j * 64;
-  }
-  auto mpix = [&](int row) -> int {
-    if (!a.strip64) return m0 + row;
-    const int rr = (m0 & 255) + row;
-    return sbase + (rr >> 6) * a.W + (rr & 63);
-  };
-  if (a.out_nchw) {
-    float* y = (float*)a.y;
-    const int HW = a.H * a.W;
-    for (int idx = tid; idx < ROWS * BN; idx += NT) {
-      const int row = idx % ROWS, col = idx / ROWS;
-      const int m = mpix(row), n = n0 + col;
-      if (m0 + row >= a.M || n >= a.Cout_real) continue;
-      float v = Cs[row * CSTR + col] + (a.bias ? a.bias[n] : 0.f);
-      v = act_apply(v, a.act, a.slope) * row_alpha(a, m);
-      v = v * (a.aff_scale ? a.aff_scale[n] : 1.f) + (a.aff_shift ? a.aff_shift[n] : 0.f);
-      const int img = m / HW, pix = m - img * HW;
-      y[((size_t)img * a.Cout_real + n) * HW + pix] = v;
-    }
-    return;
-  }
-  constexpr int CG = BN / 8;  // 8-channel groups per row
-  constexpr int IT = ROWS * CG / NT;  // groups per thread
-  static_assert(ROWS * CG % NT == 0, "epilogue tiling");
-  constexpr int NV = SZ == 2 ? 1 : 2;  // 16-B loads per 8-channel group
-  const __amdgpu_buffer_rsrc_t gr = make_rsrc(a.gate, a.g_bytes);
-  const __amdgpu_buffer_rsrc_t rr = make_rsrc(a.res, a.r_bytes);
-  const __amdgpu_buffer_rsrc_t rr2 = make_rsrc(a.res2, a.r2_bytes);
-  // per batch of IB groups: first issue every gate / residual load (range-checked buffer
-  // loads: invalid groups read zeros) so their HBM latency overlaps, then compute + store.
-  constexpr int IB = (SZ == 2 ? 4 : 2) < IT ? (SZ == 2 ? 4 : 2) : IT;  // groups per load batch
-  static_assert(IT % IB == 0, "epilogue batch");
-  // colsum: this thread's 8 channels (cg is fixed: NT % CG == 0) summed over its rows, of the
-  // value as stored (bf16-rounded); reduced over the wave's lanes of the same cg below.
-  float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  static_assert(NT % CG == 0 && 64 % CG == 0, "colsum lane map");
-#pragma unroll 1
-  for (int it0 = 0; it0 < IT; it0 += IB) {
-  u32x4 gv[IB][NV], rv1[IB][NV], rv2[IB][NV];
-#pragma unroll
-  for (int ib = 0; ib < IB; ++ib) {
-    const int it = ib;
-    const int idx = tid + (it0 + ib) * NT;
-    const int row = idx / CG, cg = idx % CG;
-    const int m = mpix(row), n = n0 + cg * 8;
-    const bool ok = m0 + row < a.M && n < a.Cout;
-    const bool okr = ok && n < a.rcols;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      if (a.gate) {
-        const bool gok = ok && (a.gate_mode != 2 || (n >= a.gcol0 && n < a.gcol1));
-        gv[it][v] = buf_load16(gr, gok ? (uint32_t)(((size_t)m * a.ldg + a.gcoff + n) * SZ) + 16u * v : SR_OOB);
-      }
-      if (a.res) rv1[it][v] = buf_load16(rr, okr ? (uint32_t)(((size_t)m * a.ldr + a.rcoff + n) * SZ) + 16u * v : SR_OOB);
-      if (a.res2)
-        rv2[it][v] = buf_load16(rr2, okr ? (uint32_t)(((size_t)m * a.ldr2 + a.r2coff + n) * SZ) + 16u * v : SR_OOB);
-    }
-  }
-  auto unpack = [&](const u32x4* q, float* o) {
-    if constexpr (SZ == 2) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        o[2 * j] = bf16_to_f32(q[0][j] & 0xffff);
-        o[2 * j + 1] = bf16_to_f32(q[0][j] >> 16);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { o[j] = __uint_as_float(q[0][j]); o[4 + j] = __uint_as_float(q[NV - 1][j]); }
-    }
-  };
-#pragma unroll
-  for (int it = 0; it < IB; ++it) {
-    const int idx = tid + (it0 + it) * NT;
-    const int row = idx / CG, cg = idx % CG;
-    const int m = mpix(row), n = n0 + cg * 8;
-    if (m0 + row >= a.M || n >= a.Cout) continue;
-    float v[8];
-    const f32x4 c0 = *(const f32x4*)(Cs + row * CSTR + cg * 8);
-    const f32x4 c1 = *(const f32x4*)(Cs + row * CSTR + cg * 8 + 4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { v[j] = c0[j]; v[4 + j] = c1[j]; }
-    if (a.bias) {
-      const f32x4 b0 = *(const f32x4*)(a.bias + n);
-      const f32x4 b1 = *(const f32x4*)(a.bias + n + 4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { v[j] += b0[j]; v[4 + j] += b1[j]; }
-    }
-    if (a.aux) {  // activation side output (act_aux_n: GELU' for GELU, which the backward's gate reads)
-      float ax[8];
-      act_aux_n(v, ax, a.act, a.slope);
-      const size_t da = (size_t)m * a.ldy + a.ycoff + n;
-      if constexpr (SZ == 2) {
-        u32x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = pack_bf16x2(ax[2 * j], ax[2 * j + 1]);
-        *(u32x4*)((bf16_t*)a.aux + da) = o;
-      } else {
-        *(f32x4*)((float*)a.aux + da) = f32x4{ax[0], ax[1], ax[2], ax[3]};
-        *(f32x4*)((float*)a.aux + da + 4) = f32x4{ax[4], ax[5], ax[6], ax[7]};
-      }
-    } else {
-      act_apply_n(v, a.act, a.slope);
-    }
-    if (a.gate && a.gate_mode != 2) {
-      float g[8];
-      unpack(gv[it], g);
-      if (a.gate_mode == 1) {  // the stored GELU' (the forward's aux)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] *= g[j];
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] *= (g[j] > 0.f ? 1.f : a.gate_slope);
-      }
-    }
-    {
-      const float al = row_alpha(a, m);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] *= al;
-    }
-    if (a.res && n < a.rcols) {
-      float rv[8];
-      unpack(rv1[it], rv);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = a.beta * rv[j] + v[j];
-    }
-    if (a.res2 && n < a.rcols) {
-      float rv[8];
-      unpack(rv2[it], rv);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = a.beta2 * rv[j] + v[j];
-    }
-    if (a.gate && a.gate_mode == 2 && n >= a.gcol0 && n < a.gcol1) {
-      float g[8];
-      unpack(gv[it], g);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] *= (g[j] > 0.f ? 1.f : a.gate_slope);
-    }
-    size_t dst;  // element offset of the 8-channel group
-    if (a.out_ps == 0) {
-      dst = (size_t)m * a.ldy + a.ycoff + n;
-    } else {
-      const int r = a.out_ps;
-      const int s = (int)fdiv((uint32_t)n, a.fd_cps);
-      const int c = n - s * a.fd_cps.d;
-      const int si = s / r, sj = s - (s / r) * r;
-      const int xq = (int)fdiv((uint32_t)m, a.fd_W);
-      const int xx = m - xq * a.W;  // xq = n*H + y
-      dst = ((size_t)(xq * r + si) * (a.W * r) + xx * r + sj) * a.ldy + a.ycoff + c;
-    }
-    if constexpr (SZ == 2) {
-      u32x4 o;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = pack_bf16x2(v[2 * j], v[2 * j + 1]);
-      *(u32x4*)((bf16_t*)a.y + dst) = o;
-      if (a.colsum) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          cs[2 * j] += bf16_to_f32(o[j] & 0xffff);
-          cs[2 * j + 1] += bf16_to_f32(o[j] >> 16);
-        }
-      }
-    } else {
-      *(f32x4*)((float*)a.y + dst) = f32x4{v[0], v[1], v[2], v[3]};
-      *(f32x4*)((float*)a.y + dst + 4) = f32x4{v[4], v[5], v[6], v[7]};
-      if (a.colsum) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) cs[j] += v[j];
-      }
-    }
-  }
-  }
-  if (a.colsum) {
-    // lanes l, l ^ CG, l ^ 2CG, ... hold the same 8 channels: fixed-order butterfly, then
-    // lane cg writes row (m0 / ROWS) * (NT / 64) + wave of the [parts][Cout] partial matrix.
-    const int lane = tid & 63;
-#pragma unroll
-    for (int off = CG; off < 64; off <<= 1)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) cs[j] += __shfl_xor(cs[j], off, 64);
-    const int n = n0 + lane * 8;
-    if (lane < CG && n < a.Cout) {
-      float* dstp = a.colsum + (size_t)((m0 / ROWS) * (NT / 64) + (tid >> 6)) * a.Cout + n;
-      *(f32x4*)dstp = f32x4{cs[0], cs[1], cs[2], cs[3]};
-      *(f32x4*)(dstp + 4) = f32x4{cs[4], cs[5], cs[6], cs[7]};
-    }
-  }
-}
 
 template <typename T, int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(256, 2) void conv3x3_fwd_kernel(FwdArgs a) {
@@ -468,8 +184,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_fwd_kernel(FwdArgs a) {
 // so the XOR swizzle of the ds_read_b128 fragment reads is applied to the per-lane SOURCE
 // chunk (rule 21).  Epilogue: the fp32 tile is staged through LDS in two 128-row halves.
 // ------------------------------------------------------------------------------------
-constexpr int BIG_STAGE = 65536;
-
 __global__ __launch_bounds__(512) void conv3x3_fwd_big_kernel(FwdArgs a) {
   constexpr int MI = 8, NI = 4;
   constexpr int CSTR = 256 + 4;
@@ -619,12 +333,6 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_big_kernel(FwdArgs a) {
 // (two barriers for the lagging group); its slot is re-filled >= 4 phases after its last
 // read.  Fragments: A 32 VGPR (one half), B 2 x 16 VGPR (both halves), acc 128 VGPR.
 // ------------------------------------------------------------------------------------
-SR_DEV void pp_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 template <bool FAST>
 __global__ __launch_bounds__(512) void conv3x3_fwd_pp_kernel(FwdArgs a) {
   constexpr int CSTR = 256 + 4;
@@ -1516,556 +1224,6 @@ __global__ __launch_bounds__(512) void conv3x3_fwd_pph_kernel(FwdArgs a) {
 }
 
 // ------------------------------------------------------------------------------------
-// linear_wk_kernel<E>: 1x1 convs streamed over K -- the SwinIR fc2 forward (360 -> 184), the fc1 /
-// qkv dgrads (360 / 576 -> 184), and (K <= 192) the fc2 / proj dgrads and proj forward.  A block owns
-// 128 tokens x one 192-wide tile of the output channels (Cout <= 576: the tiles of one token tile are
-// consecutive blocks, so its token rows are read from L2 by the second) and streams K in 64-wide steps
-// through two LDS stages (LDS-DMA of the token tile [128][128 B] and the weight tile [192][128 B], both
-// K-contiguous, chunk ^ (row & 7) swizzle; 40 KB a stage, so two blocks share a CU).  C = W . X^T as in
-// conv3x3_lin_kernel: the weight rows are permuted on load (32-row group p, tile t, row r -> channel
-// 32p + 8(r/4) + 4t + r%4), so a lane ends with 8 consecutive channels of one token and stores them as
-// one 16-B vector with the fused epilogue.  4 waves (2 channel x 2 token halves), each 96 channels x
-// 64 tokens (6 x 4 accumulator tiles).  (The 64-token lin kernel it replaces on wide K re-read the
-// whole weight image per 64 tokens -- 434 MB of L2 reads on the qkv dgrad -- and staged all of K
-// before its first MFMA.)
-// E: conv3x3_lin_kernel's epilogue codes (bits 0-1 act, 2-3 gate 1 / 2 pre-residual, 4 res, 6 aux, 7
-// row scale) for 0 (plain), 8 (GELU' gate: fc2 dgrad), 16 (residual), 67 (GELU + pre-activation aux:
-// fc1 forward), 144 (residual + row scale); the bias
-// (GEMM column order), alpha and beta always.
-// ------------------------------------------------------------------------------------
-template <int E>
-__global__ __launch_bounds__(256, 2) void linear_wk_kernel(FwdArgs a) {
-  constexpr int XI = 128 * 128, WI = 192 * 128, STAGE = XI + WI;
-  constexpr int ACT = E & EPI_ACT, GATE = (E >> EPI_GATE_SHIFT) & EPI_GATE;
-  constexpr bool RES = (E & EPI_RES) != 0, AUX = (E & EPI_AUX) != 0, RSC = (E & LIN_RSC) != 0;
-  static_assert(GATE != 3 && (E & ~(EPI_ACT | (EPI_GATE << EPI_GATE_SHIFT) | EPI_RES | EPI_AUX | LIN_RSC)) == 0,
-                "linear_wk: epilogue subset");
-  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = w >> 1, wc = w & 1;
-  const int nct = (a.Cout + 191) / 192;  // output-channel tiles (consecutive blocks)
-  const int bt = (int)xcd_remap(blockIdx.x, gridDim.x);
-  const int tt = bt / nct, ct = bt - tt * nct;
-  const int m0 = tt * 128, n0 = ct * 192;
-  const int K = a.Cin, nk = (K + 63) >> 6;
-  const __amdgpu_buffer_rsrc_t xr = make_rsrc(a.x, a.x_bytes);
-  const __amdgpu_buffer_rsrc_t wrs = make_rsrc(a.w, a.w_bytes);
-
-  // DMA pieces of 64 lanes = 8 rows x 8 chunks: per stage 16 token pieces then 24 weight pieces,
-  // wave w taking pieces w, w + 4, ...; lane: row rl of the piece, physical chunk pc = logical lc ^ rl
-  const int rl = lane >> 3, lc = (lane & 7) ^ rl;
-  int wch[6];  // source weight channel of this lane's row in weight pieces q = 4..9
-#pragma unroll
-  for (int q = 4; q < 10; ++q) {
-    const int row = (w + 4 * q - 16) * 8 + rl;
-    const int t = (row >> 4) & 1, r = row & 15;
-    wch[q - 4] = n0 + (row >> 5) * 32 + 8 * (r >> 2) + 4 * t + (r & 3);
-  }
-  auto issue = [&](int ks, int stg) {
-    char* st = smem + stg * STAGE;
-    const int kc = ks * 8 + lc;
-    const bool kv = kc * 8 < K;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int p = w + 4 * q, m = m0 + p * 8 + rl;
-      glds16(xr, st + p * 1024, (kv && m < a.M) ? (uint32_t)((m * a.ldx + a.xcoff + kc * 8) * 2) : SR_OOB);
-    }
-#pragma unroll
-    for (int q = 4; q < 10; ++q) {
-      const int p = w + 4 * q - 16, ch = wch[q - 4];
-      glds16(wrs, st + XI + p * 1024, (kv && ch < a.Cout) ? (uint32_t)((ch * a.ldw + kc * 8) * 2) : SR_OOB);
-    }
-  };
-
-  const int c16 = lane & 15, g = lane >> 4;
-  f32x4 acc[6][4];
-#pragma unroll
-  for (int i = 0; i < 6; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto compute = [&](int stg) {
-    const char* Xs = smem + stg * STAGE;
-    const char* Ws = Xs + XI;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int phys = ((kk * 4 + g) ^ (c16 & 7)) << 4;  // every fragment row has row & 7 == c16 & 7
-      u32x4 fa[6], fb[4];
-#pragma unroll
-      for (int i = 0; i < 6; ++i) fa[i] = *(const u32x4*)(Ws + (wr * 96 + i * 16 + c16) * 128 + phys);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) fb[j] = *(const u32x4*)(Xs + (wc * 64 + j * 16 + c16) * 128 + phys);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(s16x8, fa[i]),
-                                                              __builtin_bit_cast(s16x8, fb[j]), acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    }
-  };
-
-  issue(0, 0);
-  for (int ks = 0; ks < nk; ++ks) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    pp_barrier();  // step ks landed for every wave; step ks - 1's stage is free
-    if (ks + 1 < nk) issue(ks + 1, (ks + 1) & 1);
-    compute(ks & 1);
-  }
-
-  // ---- epilogue: pair P (tiles 2P, 2P + 1) gives channels n = n0 + (3 wr + P) * 32 + 8g .. + 7 of
-  // token m0 + 64 wc + 16 j + c16
-  const __amdgpu_buffer_rsrc_t rr = make_rsrc(a.res, a.r_bytes);
-  const __amdgpu_buffer_rsrc_t gr = make_rsrc(a.gate, a.g_bytes);
-  const size_t ybytes = (size_t)a.M * a.ldy * 2;
-  const __amdgpu_buffer_rsrc_t yr = make_rsrc(a.y, ybytes < 0x80000000ull ? (uint32_t)ybytes : 0x7fffffffu);
-  const __amdgpu_buffer_rsrc_t ar = make_rsrc(a.aux, AUX ? (ybytes < 0x80000000ull ? (uint32_t)ybytes : 0x7fffffffu) : 0u);
-  const __amdgpu_buffer_rsrc_t br = make_rsrc(a.bias, a.bias ? (uint32_t)a.Cout * 4u : 0u);
-  float alpha_blk = a.alpha;
-  if constexpr (RSC) alpha_blk = a.alpha * a.row_scale[fdiv((uint32_t)m0, a.fd_hw)];
-  u32x4 rv[3][4], gv[3][4];
-  float bv[3][8];
-#pragma unroll
-  for (int P = 0; P < 3; ++P) {
-    const int n = n0 + (3 * wr + P) * 32 + 8 * g;
-    const u32x4 b0 = buf_load16(br, (uint32_t)n * 4u), b1 = buf_load16(br, (uint32_t)n * 4u + 16u);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { bv[P][r] = __uint_as_float(b0[r]); bv[P][4 + r] = __uint_as_float(b1[r]); }
-    if constexpr (GATE != 0) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int m = m0 + wc * 64 + j * 16 + c16;
-        gv[P][j] = buf_load16(gr, (n < a.Cout && m < a.M) ? (uint32_t)(((size_t)m * a.ldg + a.gcoff + n) * 2) : SR_OOB);
-      }
-    }
-    if constexpr (RES) {
-      const bool rok = n < a.Cout && n < a.rcols;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int m = m0 + wc * 64 + j * 16 + c16;
-        rv[P][j] = buf_load16(rr, (rok && m < a.M) ? (uint32_t)(((size_t)m * a.ldr + a.rcoff + n) * 2) : SR_OOB);
-      }
-    }
-  }
-#pragma unroll
-  for (int P = 0; P < 3; ++P) {
-    const int n = n0 + (3 * wr + P) * 32 + 8 * g;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int m = m0 + wc * 64 + j * 16 + c16;
-      float v[8];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        v[r] = acc[2 * P][j][r] + bv[P][r];
-        v[4 + r] = acc[2 * P + 1][j][r] + bv[P][4 + r];
-      }
-      if constexpr (AUX) {  // activation side output (act_aux_n: GELU' for GELU)
-        float ax[8];
-        act_aux_n(v, ax, ACT, a.slope);
-        u32x4 o;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[q] = pack_bf16x2(ax[2 * q], ax[2 * q + 1]);
-        __builtin_amdgcn_raw_buffer_store_b128(o, ar, (n < a.Cout && m < a.M) ? (uint32_t)(((size_t)m * a.ldy + a.ycoff + n) * 2) : SR_OOB, 0, 0);
-      } else if constexpr (ACT == 1) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = v[q] > 0.f ? v[q] : 0.f;
-      } else if constexpr (ACT == 2) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = v[q] > 0.f ? v[q] : v[q] * a.slope;
-      } else if constexpr (ACT == 3) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = gelu_exact(v[q]);
-      }
-      if constexpr (GATE != 0) {
-        float gf[8];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          gf[2 * q] = bf16_to_f32(gv[P][j][q] & 0xffff);
-          gf[2 * q + 1] = bf16_to_f32(gv[P][j][q] >> 16);
-        }
-        if constexpr (GATE == 1) {
-#pragma unroll
-          for (int q = 0; q < 8; ++q) v[q] *= gf[q] > 0.f ? 1.f : a.gate_slope;
-        } else {  // the stored GELU' (the forward's aux)
-#pragma unroll
-          for (int q = 0; q < 8; ++q) v[q] *= gf[q];
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] *= alpha_blk;
-      if constexpr (RES) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          v[2 * q] += a.beta * bf16_to_f32(rv[P][j][q] & 0xffff);
-          v[2 * q + 1] += a.beta * bf16_to_f32(rv[P][j][q] >> 16);
-        }
-      }
-      u32x4 o;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) o[q] = pack_bf16x2(v[2 * q], v[2 * q + 1]);
-      __builtin_amdgcn_raw_buffer_store_b128(o, yr, (n < a.Cout && m < a.M) ? (uint32_t)(((size_t)m * a.ldy + a.ycoff + n) * 2) : SR_OOB, 0, 0);
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------
-// conv3x3_lin_kernel<MT>: 1x1 convs (nn.Linear over NHWC tokens: SwinIR qkv / proj / fc1 /
-// fc2 and their dgrads, DCN column GEMMs) with a short K (<= 576).  These GEMMs are
-// HBM-bound (AI ~ 100-150 FLOP/B); the 2-D tiled kernels re-read the token rows once per
-// N tile and pay a full prologue / epilogue per 2-3 K-steps.  Here a block loads its MT
-// token rows x all K ONCE into LDS (LDS-DMA, [K/64][MT][128 B] XOR-swizzled) and then
-// sweeps every output channel, 128 per pass (32 per wave): W fragments come from L2
-// straight into registers, X^T fragments from LDS, C = W x X^T so each lane ends with 8
-// consecutive channels of one token (the W tile rows are permuted on load: tile t row r ->
-// channel 8(r/4) + 4t + r%4) and stores 16 B directly, with the fused epilogue (bias,
-// activation, pre-activation side output, gate, alpha, residuals) in registers.
-// ------------------------------------------------------------------------------------
-// E >= 0: the epilogue fixed at compile time (bits 0-1 act, 2-3 gate 0 none / 1 pre-residual
-// (g > 0 ? 1 : gate_slope) / 2 pre-residual GELU'(g) / 3 post-residual on gcol0..gcol1, 4 res,
-// 5 res2, 6 aux, 7 row_scale, uniform per block: H*W % MT == 0): its operand loads for a pass are
-// issued before the pass's MFMAs, so they land under them; E = -1: run-time flags, loads next to
-// their use (every combination).
-template <int MT, int MAXCG, int NPASS, int E, bool LN = false>
-__global__ __launch_bounds__(256, 2) void conv3x3_lin_kernel(FwdArgs a) {
-  constexpr int NMT = MT / 16;  // token tiles per wave (every wave covers all MT tokens)
-  constexpr bool CE = E >= 0;
-  constexpr int ACT = E & EPI_ACT, GATE = (E >> EPI_GATE_SHIFT) & EPI_GATE;
-  constexpr bool RES = (E & EPI_RES) != 0, RES2 = (E & EPI_RES2) != 0, AUX = (E & EPI_AUX) != 0, RSC = (E & LIN_RSC) != 0;
-  __shared__ __attribute__((aligned(16))) char smem[MAXCG * MT * 128];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int g = lane >> 4, c16 = lane & 15;
-  const int m0 = (int)xcd_remap(blockIdx.x, gridDim.x) * MT;
-  const int K = a.Cin, KC = K >> 3;  // 16-B chunks of a token row
-  const int CG = (K + 63) >> 6;      // 128-B chunk groups
-  const __amdgpu_buffer_rsrc_t xr = make_rsrc(a.x, a.x_bytes);
-  const __amdgpu_buffer_rsrc_t wr = make_rsrc(a.w, a.w_bytes);
-
-  __shared__ float sgb[LN ? 2 * 192 : 1];  // LN: gamma, beta (channels < 192)
-  if constexpr (LN) {
-    for (int c = tid; c < 192; c += 256) {
-      sgb[c] = c < a.ln_C ? a.ln_g[c] : 0.f;
-      sgb[192 + c] = c < a.ln_C ? a.ln_b[c] : 0.f;
-    }
-  }
-  // ---- stage the MT x K token tile: piece p = (chunk group cg, 8-row group rg)
-  {
-    const int npieces = CG * (MT / 8);
-    const int rl = lane >> 3, pc = lane & 7;
-    const int lc = pc ^ rl;  // logical chunk this lane fetches (row & 7 == rl)
-    for (int p = w; p < npieces; p += 4) {
-      const int cg = p / (MT / 8), rg = p - cg * (MT / 8);
-      const int row = rg * 8 + rl, m = m0 + row, ch = cg * 8 + lc;
-      const bool v = m < a.M && ch < KC;
-      glds16(xr, smem + (cg * MT + rg * 8) * 128, v ? (uint32_t)(((size_t)m * a.ldx + a.xcoff + ch * 8) * 2) : SR_OOB);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-  if constexpr (LN) {
-    // LayerNorm of the staged rows in place (fp32 statistics, two lanes per row over alternate
-    // 16-B chunks held in registers: one LDS read per chunk), gamma / beta from LDS, the
-    // normalised rows also stored to ln_out with the row mean / rstd: the standalone LN kernel's
-    // read of x and this kernel's read of its output become one read
-    constexpr int MAXQ = MAXCG * 4;  // chunks per lane (2 lanes per row, MAXCG * 8 chunks)
-    const int row = tid >> 1, half = tid & 1, m = m0 + row;
-    auto chunk_ptr = [&](int ch) -> u32x4* {
-      return (u32x4*)(smem + (ch >> 3) * MT * 128 + row * 128 + (((ch & 7) ^ (row & 7)) << 4));
-    };
-    u32x4 raw[MAXQ];
-    float sm = 0.f;
-#pragma unroll
-    for (int q = 0; q < MAXQ; ++q) {
-      const int ch = half + 2 * q;
-      raw[q] = ch < KC ? *chunk_ptr(ch) : u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = ch * 8 + 2 * j;
-        sm += (c < a.ln_C ? bf16_to_f32(raw[q][j] & 0xffff) : 0.f) + (c + 1 < a.ln_C ? bf16_to_f32(raw[q][j] >> 16) : 0.f);
-      }
-    }
-    sm += __shfl_xor(sm, 1);
-    const float mu = sm / a.ln_C;
-    float sq = 0.f;
-#pragma unroll
-    for (int q = 0; q < MAXQ; ++q) {
-      const int ch = half + 2 * q;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = ch * 8 + 2 * j;
-        const float d0 = c < a.ln_C ? bf16_to_f32(raw[q][j] & 0xffff) - mu : 0.f;
-        const float d1 = c + 1 < a.ln_C ? bf16_to_f32(raw[q][j] >> 16) - mu : 0.f;
-        sq += d0 * d0 + d1 * d1;
-      }
-    }
-    sq += __shfl_xor(sq, 1);
-    const float rs = rsqrtf(sq / a.ln_C + a.ln_eps);
-    __syncthreads();  // gamma / beta staged (below the token DMA wait) by every wave
-#pragma unroll
-    for (int q = 0; q < MAXQ; ++q) {
-      const int ch = half + 2 * q;
-      if (ch >= KC) break;
-      float o[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int c = ch * 8 + j;
-        const float xv = bf16_to_f32((raw[q][j >> 1] >> (16 * (j & 1))) & 0xffff);
-        o[j] = c < a.ln_C ? (xv - mu) * rs * sgb[c] + sgb[192 + c] : 0.f;
-      }
-      u32x4 r;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) r[j] = pack_bf16x2(o[2 * j], o[2 * j + 1]);
-      *chunk_ptr(ch) = r;
-      if (m < a.M) *(u32x4*)((bf16_t*)a.ln_out + (size_t)m * K + ch * 8) = r;
-    }
-    if (half == 0 && m < a.M) {
-      a.ln_mean[m] = mu;
-      a.ln_rstd[m] = rs;
-    }
-    __syncthreads();
-  }
-
-  const __amdgpu_buffer_rsrc_t gr = make_rsrc(a.gate, a.g_bytes);
-  const __amdgpu_buffer_rsrc_t rr = make_rsrc(a.res, a.r_bytes);
-  const __amdgpu_buffer_rsrc_t rr2 = make_rsrc(a.res2, a.r2_bytes);
-  // output descriptors sized to the output (a lane past it stores at SR_OOB = 2^31, which must
-  // fall outside the descriptor to be dropped)
-  const size_t ybytes = (size_t)a.M * a.ldy * 2;
-  const uint32_t yb = ybytes < 0x80000000ull ? (uint32_t)ybytes : 0x7fffffffu;
-  const __amdgpu_buffer_rsrc_t yr = make_rsrc(a.y, yb);
-  const __amdgpu_buffer_rsrc_t ar = make_rsrc(a.aux, a.aux ? yb : 0u);
-  // compile-time epilogue: the block's row scale (all MT tokens in one image)
-  float alpha_blk = a.alpha;
-  if constexpr (CE && RSC) alpha_blk = a.alpha * a.row_scale[fdiv((uint32_t)m0, a.fd_hw)];
-  const int nkk = (K + 31) >> 5;
-  constexpr int npass = NPASS;  // (Cout + 127) / 128, fixed so the pass loop unrolls: the
-  // compiler's own vmcnt waits are then exact (a rolled loop waited vmcnt(0) for the W loads,
-  // i.e. for the previous pass's output stores too)
-  constexpr int MAXKK = MAXCG * 2;
-  // W fragments of a whole pass (all K) in registers, the next pass's loads in flight while the
-  // current pass computes: an L2 round trip per K-step would otherwise set the pace
-  u32x4 wb[MAXKK][2];
-  auto wload_pass = [&](int pass) {
-    const int r0 = pass * 128 + w * 32 + 8 * (c16 >> 2) + (c16 & 3);
-    const bool wv0 = r0 < a.Cout, wv1 = r0 + 4 < a.Cout;
-#pragma unroll
-    for (int kk = 0; kk < MAXKK; ++kk) {
-      const int k = kk * 32 + 8 * g;
-      const bool kv = kk < nkk && k < K;
-      wb[kk][0] = buf_load16(wr, (wv0 && kv) ? (uint32_t)((r0 * a.ldw + k) * 2) : SR_OOB);
-      wb[kk][1] = buf_load16(wr, (wv1 && kv) ? (uint32_t)(((r0 + 4) * a.ldw + k) * 2) : SR_OOB);
-    }
-  };
-  // the bias of every pass up front: a load in the epilogue would queue behind the next pass's
-  // W loads (vector memory completes in order), exposing their latency per pass
-  // (buffer loads, no branch: a missing bias or channels past Cout read zeros)
-  const __amdgpu_buffer_rsrc_t br = make_rsrc(a.bias, a.bias ? (uint32_t)a.Cout * 4u : 0u);
-  float bva[NPASS][8];
-#pragma unroll
-  for (int pass = 0; pass < NPASS; ++pass) {
-    const uint32_t n = (uint32_t)(pass * 128 + w * 32 + 8 * g);
-    const u32x4 b0 = buf_load16(br, n * 4u), b1 = buf_load16(br, n * 4u + 16u);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { bva[pass][j] = __uint_as_float(b0[j]); bva[pass][4 + j] = __uint_as_float(b1[j]); }
-  }
-  wload_pass(0);
-#pragma unroll
-  for (int pass = 0; pass < npass; ++pass) {
-    const int nb = pass * 128 + w * 32;  // this wave's 32 channels (tile t row r -> nb + 8(r/4) + 4t + r%4)
-    const int n = nb + 8 * g;
-    const bool nok = n < a.Cout;
-    // compile-time epilogue operands of this pass, issued now so they land under the MFMAs
-    // (out-of-range lanes read zeros: buffer offsets past the descriptor)
-    u32x4 gv[NMT], rv[NMT], rv2[NMT];
-    if constexpr (CE) {
-      const bool gok = nok && (GATE != 3 || (n >= a.gcol0 && n < a.gcol1));
-      const bool rok = nok && n < a.rcols;
-#pragma unroll
-      for (int i = 0; i < NMT; ++i) {
-        const int m = m0 + i * 16 + c16;
-        const bool mok = m < a.M;
-        if constexpr (GATE != 0)
-          gv[i] = buf_load16(gr, (mok && gok) ? (uint32_t)(((size_t)m * a.ldg + a.gcoff + n) * 2) : SR_OOB);
-        if constexpr (RES)
-          rv[i] = buf_load16(rr, (mok && rok) ? (uint32_t)(((size_t)m * a.ldr + a.rcoff + n) * 2) : SR_OOB);
-        if constexpr (RES2)
-          rv2[i] = buf_load16(rr2, (mok && rok) ? (uint32_t)(((size_t)m * a.ldr2 + a.r2coff + n) * 2) : SR_OOB);
-      }
-    }
-    f32x4 acc[NMT][2];
-#pragma unroll
-    for (int i = 0; i < NMT; ++i) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kk = 0; kk < MAXKK; ++kk) {
-      // a guarded body, not a break: with MAXKK 12 / 18 (wide K) a break left the loop rolled and
-      // the W fragments indexed dynamically (in scratch)
-      if (kk < nkk) {
-      const int ch = kk * 4 + g;  // logical 16-B chunk of the X^T fragment
-      // [cg][row][128 B], physical chunk = logical ^ (row & 7); row & 7 == c16 & 7 for all i
-      const char* base = smem + (ch >> 3) * MT * 128 + c16 * 128 + ((((ch & 7) ^ (c16 & 7))) << 4);
-      // all NMT fragments of the K step first (in flight together), then the MFMAs
-      u32x4 xf[NMT];
-#pragma unroll
-      for (int i = 0; i < NMT; ++i) xf[i] = *(const u32x4*)(base + i * 16 * 128);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < NMT; ++i) {
-        acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(s16x8, wb[kk][0]),
-                                                            __builtin_bit_cast(s16x8, xf[i]), acc[i][0], 0, 0, 0);
-        acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(s16x8, wb[kk][1]),
-                                                            __builtin_bit_cast(s16x8, xf[i]), acc[i][1], 0, 0, 0);
-      }
-      }
-    }
-    // the next pass's W fragments load while this pass's epilogue runs
-    if (pass + 1 < npass) wload_pass(pass + 1);
-    // ---- epilogue: lane (g, c16) holds channels nb + 8g .. +7 of token m0 + 16i + c16 and
-    // stores them as one 16-B vector (4 lanes cover 64 contiguous bytes of a token row;
-    // staging whole rows through LDS measured slower: 78 -> 95 us on the qkv shape)
-    const float* bv = bva[pass];
-    if constexpr (CE) {
-      // branch-free over lanes: stores of out-of-range lanes go past the buffer descriptor
-#pragma unroll
-      for (int i = 0; i < NMT; ++i) {
-        const int m = m0 + i * 16 + c16;
-        const bool ok = nok && m < a.M;
-        float v[8];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { v[r] = acc[i][0][r] + bv[r]; v[4 + r] = acc[i][1][r] + bv[4 + r]; }
-        if constexpr (AUX) {  // activation side output (act_aux_n: GELU' for GELU)
-          float ax[8];
-          act_aux_n(v, ax, ACT, a.slope);
-          u32x4 o;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) o[j] = pack_bf16x2(ax[2 * j], ax[2 * j + 1]);
-          __builtin_amdgcn_raw_buffer_store_b128(o, ar,
-                                                 ok ? (uint32_t)(((size_t)m * a.ldy + a.ycoff + n) * 2) : SR_OOB, 0, 0);
-        } else if constexpr (ACT == 1) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = v[j] > 0.f ? v[j] : 0.f;
-        } else if constexpr (ACT == 2) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = v[j] > 0.f ? v[j] : v[j] * a.slope;
-        } else if constexpr (ACT == 3) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = gelu_exact(v[j]);
-        }
-        float gf[8];
-        if constexpr (GATE != 0) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            gf[2 * j] = bf16_to_f32(gv[i][j] & 0xffff);
-            gf[2 * j + 1] = bf16_to_f32(gv[i][j] >> 16);
-          }
-        }
-        if constexpr (GATE == 1) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] *= gf[j] > 0.f ? 1.f : a.gate_slope;
-        } else if constexpr (GATE == 2) {  // the stored GELU' (the forward's aux)
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] *= gf[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] *= alpha_blk;
-        if constexpr (RES) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            v[2 * j] += a.beta * bf16_to_f32(rv[i][j] & 0xffff);
-            v[2 * j + 1] += a.beta * bf16_to_f32(rv[i][j] >> 16);
-          }
-        }
-        if constexpr (RES2) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            v[2 * j] += a.beta2 * bf16_to_f32(rv2[i][j] & 0xffff);
-            v[2 * j + 1] += a.beta2 * bf16_to_f32(rv2[i][j] >> 16);
-          }
-        }
-        if constexpr (GATE == 3) {
-          if (n >= a.gcol0 && n < a.gcol1) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] *= gf[j] > 0.f ? 1.f : a.gate_slope;
-          }
-        }
-        u32x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = pack_bf16x2(v[2 * j], v[2 * j + 1]);
-        __builtin_amdgcn_raw_buffer_store_b128(o, yr,
-                                               ok ? (uint32_t)(((size_t)m * a.ldy + a.ycoff + n) * 2) : SR_OOB, 0, 0);
-      }
-      continue;
-    }
-    if (!nok) continue;
-#pragma unroll
-    for (int i = 0; i < NMT; ++i) {  // fully unrolled: acc must stay register-indexed (no scratch)
-      const int m = m0 + i * 16 + c16;
-      if (m >= a.M) continue;
-      u32x4 gv1, rv1, rv21;
-      const bool rok = n < a.rcols;
-      if (a.gate) gv1 = buf_load16(gr, (a.gate_mode != 2 || (n >= a.gcol0 && n < a.gcol1))
-                                           ? (uint32_t)(((size_t)m * a.ldg + a.gcoff + n) * 2) : SR_OOB);
-      if (a.res) rv1 = buf_load16(rr, rok ? (uint32_t)(((size_t)m * a.ldr + a.rcoff + n) * 2) : SR_OOB);
-      if (a.res2) rv21 = buf_load16(rr2, rok ? (uint32_t)(((size_t)m * a.ldr2 + a.r2coff + n) * 2) : SR_OOB);
-      float v[8];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { v[r] = acc[i][0][r] + bv[r]; v[4 + r] = acc[i][1][r] + bv[4 + r]; }
-      if (a.aux) {  // activation side output (act_aux_n: GELU' for GELU)
-        float ax[8];
-        act_aux_n(v, ax, a.act, a.slope);
-        u32x4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = pack_bf16x2(ax[2 * j], ax[2 * j + 1]);
-        *(u32x4*)((bf16_t*)a.aux + (size_t)m * a.ldy + a.ycoff + n) = o;
-      } else {
-        act_apply_n(v, a.act, a.slope);
-      }
-      if (a.gate && a.gate_mode != 2) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float g0 = bf16_to_f32(gv1[j] & 0xffff), g1 = bf16_to_f32(gv1[j] >> 16);
-          if (a.gate_mode == 1) {  // the stored GELU'
-            v[2 * j] *= g0;
-            v[2 * j + 1] *= g1;
-          } else {
-            v[2 * j] *= g0 > 0.f ? 1.f : a.gate_slope;
-            v[2 * j + 1] *= g1 > 0.f ? 1.f : a.gate_slope;
-          }
-        }
-      }
-      const float al = row_alpha(a, m);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] *= al;
-      if (a.res) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          v[2 * j] += a.beta * bf16_to_f32(rv1[j] & 0xffff);
-          v[2 * j + 1] += a.beta * bf16_to_f32(rv1[j] >> 16);
-        }
-      }
-      if (a.res2) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          v[2 * j] += a.beta2 * bf16_to_f32(rv21[j] & 0xffff);
-          v[2 * j + 1] += a.beta2 * bf16_to_f32(rv21[j] >> 16);
-        }
-      }
-      if (a.gate && a.gate_mode == 2 && n >= a.gcol0 && n < a.gcol1) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          v[2 * j] *= bf16_to_f32(gv1[j] & 0xffff) > 0.f ? 1.f : a.gate_slope;
-          v[2 * j + 1] *= bf16_to_f32(gv1[j] >> 16) > 0.f ? 1.f : a.gate_slope;
-        }
-      }
-      u32x4 o;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = pack_bf16x2(v[2 * j], v[2 * j + 1]);
-      *(u32x4*)((bf16_t*)a.y + (size_t)m * a.ldy + a.ycoff + n) = o;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------
 // Forward / dgrad for narrow convs (Cout <= 64: RCAN / RRDB / SRResNet bodies at W 64 or
 // 128).  A block computes 256 consecutive output pixels = R = 256 / W full rows of one image
 // x all Cout channels.  Per 64-channel input chunk it stages the halo rows y0-1 .. y0+R,
@@ -2311,551 +1469,6 @@ __global__ __launch_bounds__(256, HALF ? 3 : 2) void conv3x3_fwd_halo_kernel(Fwd
 }
 
 // ------------------------------------------------------------------------------------
-// Narrow-conv forward / dgrad, row-streaming persistent form (bf16 3x3, Cin 32 or 64,
-// Cout 32 or 64, W 64 or 128: RCAN / SRResNet bodies, RRDB conv1 and dgrads into 64 ch).
-//
-// The tile kernel above loads a halo, computes and stores in one pass per block, so with one
-// wave of blocks the chip runs the three phases one after the other (RCAN conv at B 32:
-// 24 us, of which 8 us store tail and ~5 us load burst; the MFMA work is ~4.6 us per SIMD).
-// Here a block owns a band of consecutive output rows (one row = W pixels of one image; the
-// NHWC rows of all images are one contiguous sequence) and streams it: input rows live in an
-// (LA + 2)-slot LDS ring (slot = global row % S, W + 2 swizzled 128-B pixel rows, zero border
-// columns written once); row s + LA is DMA'd while row s is computed, the residual / gate
-// operands of row s are DMA'd into per-wave staging before its MFMAs (each lane reads back its
-// own 16 B), and its stores drain while later rows compute.  Rows outside an image (the 3x3
-// zero padding in y) are never read: the taps that would read them are skipped (wave-uniform
-// test per row).  Each wave keeps ALL its weights (32 output channels x 9 taps x Cin) in
-// registers for the whole band, loaded once.
-// MFMA as the DIRECT halo epilogue: C = W x X^T with row-permuted weight tiles, so each lane
-// ends with 8 consecutive channels of one pixel and stores 16 B; colsum (RCAN avg-pool)
-// partial rows per (image row, pixel wave).
-// vmcnt bookkeeping per wave: per row [NG staging pieces] [PPW row pieces] .. MFMAs ..
-// vmcnt(PPW) (staging landed) [PT stores] [NC colsum stores]; before row s the count of vector
-// memory ops younger than row s + 1's pieces is known in closed form (prologue rows, then the
-// steady state (PT + NC) + (LA - 2) * ops-per-row) and waited with a run-time vmcnt.
-// ------------------------------------------------------------------------------------
-// s_waitcnt vmcnt(n) for a run-time n (wave-uniform): the immediate is chosen by a binary
-// search over 0..63 (6 scalar branches; a linear compare chain cost ~40 cycles per step at one
-// wave per SIMD); n > 63 waits for vmcnt(63), which only waits longer.
-template <int LO, int HI>
-SR_DEV void vm_wait_bs(int n) {
-  if constexpr (LO == HI) {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LO) : "memory");
-  } else {
-    constexpr int MID = (LO + HI) / 2;
-    if (n <= MID) vm_wait_bs<LO, MID>(n);
-    else vm_wait_bs<MID + 1, HI>(n);
-  }
-}
-SR_DEV void vm_wait_dyn(int n) { vm_wait_bs<0, 63>(n < 0 ? 0 : (n > 63 ? 63 : n)); }
-
-// E (the epilogue, fixed at compile time: at one wave per SIMD every run-time branch of a
-// per-row epilogue is exposed): bits 0-1 act, 2-3 gate (0 none, 1 pre-residual (g > 0 ? 1 :
-// gate_slope), 2 pre-residual GELU'(g), 3 post-residual (g > 0 ? 1 : gate_slope) on output
-// channels gcol0..gcol1), 4 res, 5 res2, 6 aux, 7 colsum, 8 row_scale, 9 dot (with 7: the partial
-// sums are of y * dot, the dot operand staged like the residuals).
-// blocks per CU the band kernel is built for: two for the W 64 forms whose ring + staging fit
-// 80 KB of LDS and 256 registers (no second staging operand), one otherwise.  And (round 6) the RCAB
-// conv1 dgrad with the dot epilogue (656: residual + dot staging, 82 KB): not for a second band block
-// but so that it shares a CU with a side-stream ring wgrad block (78 KB) as the plain residual form
-// does -- at one block per CU (the weight image beside the ring, 154 KB) it held whole CUs against the
-// side stream and RCAN ran 35.6 vs 33.6 ms
-constexpr int band_occ(int W, int E) {
-  return W == 64 && (E == 0 || E == 1 || E == 2 || E == 4 || E == 16 || E == 128 || E == 656) ? 2 : 1;
-}
-// NWV: waves per block, 4 (one per SIMD) or 8 (two per SIMD, each with half the row's pixel
-// tiles, so one wave's epilogue and LDS waits overlap the other's MFMAs; the ring and the weight
-// image shared).  8 at W 128: RRDB 63.8 -> 61.0 ms; at W 64 (one pixel tile per wave) RCAN
-// 33.8 -> 37.0 ms, so 4 there.
-template <int CO, int W, int LA, int KH, int E, int NWV = 4>
-__global__ __launch_bounds__(NWV * 64, NWV == 8 ? 2 : band_occ(W, E)) void conv3x3_fwd_band_kernel(FwdArgs a) {
-  constexpr int ACT = E & EPI_ACT, GATE = (E >> EPI_GATE_SHIFT) & EPI_GATE;
-  constexpr bool RES = (E & EPI_RES) != 0, RES2 = (E & EPI_RES2) != 0, AUX = (E & EPI_AUX) != 0, CS = (E & BAND_CS) != 0,
-                 RSC = (E & BAND_RSC) != 0, DOT = (E & BAND_DOT) != 0, STRIP = (E & BAND_STRIP) != 0;
-  static_assert(!DOT || CS, "band: dot partials need colsum");
-  static_assert(!STRIP || (!CS && !RSC), "band: column strips carry no per-image epilogue");
-  constexpr int IR = GATE ? 1 : 0, IR2 = IR + (RES ? 1 : 0), ID = IR2 + (RES2 ? 1 : 0), NSTG = ID + (DOT ? 1 : 0);
-  static_assert(NWV == 4 || (NWV == 8 && W / 16 / (8 / (CO / 32)) >= 1), "band: a pixel tile per wave");
-  constexpr int WC = CO / 32;       // waves along output channels (32 each = 2 co tiles)
-  constexpr int WP = NWV / WC;      // waves along the row's pixels
-  constexpr int PT = W / 16 / WP;   // 16-pixel tiles per wave
-  constexpr int WPAD = W + 2;
-  constexpr int SLOT = WPAD * 128;
-  constexpr int S = LA + 2;         // ring slots: rows s-1 .. s+1 read, s+2 .. s+LA in flight
-  constexpr int PPW = W / 8 / NWV;  // 1-KB DMA pieces per wave per row
-  constexpr int NG = NSTG * PT;     // staging pieces per wave per row (gate / res / res2)
-  constexpr int NC = (CS ? 2 : 0) + (AUX ? PT : 0);  // stores after the PT output stores
-  constexpr int PPWX = PPW + (STRIP ? 1 : 0);  // + the strip's border piece (or a dummy) per wave
-  constexpr int KROW = NG + PPWX + PT + NC;           // vector memory ops per wave per row
-  // per-wave staging (none for the wide strip forms without epilogue operands, CO > 64: their LDS is
-  // the weight image's)
-  constexpr int EPI = (NSTG ? NSTG : (CO > 64 ? 0 : 1)) * PT * 1024;
-  constexpr int CIN = 32 * KH;
-  constexpr int WROW = 9 * CIN * 2;  // bytes of one output channel's weights [tap][ci]
-  constexpr int WBYTES = CO * WROW;
-  constexpr int RING = (S + 1) * SLOT + NWV * EPI;
-  // ring + one all-zero slot (the rows above / below an image read it, so the MFMA sequence has
-  // no branches) + staging; the weight image after them where both fit (WSEP: the ring prologue
-  // is issued before the weights are waited for; only forms built for one block per CU: the extra
-  // LDS would cost the W 64 forms their second block and RCAN 2.7 ms), else in the same space
-  // before the ring starts
-  constexpr bool WSEP = band_occ(W, E) == 1 && RING + WBYTES <= 160 * 1024;
-  __shared__ __attribute__((aligned(16))) char smem[WSEP ? RING + WBYTES : (RING > WBYTES ? RING : WBYTES)];
-  char* const wimg = smem + (WSEP ? RING : 0);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wc = w % WC, wp = w / WC;
-  const int g = lane >> 4, c16 = lane & 15;
-  const int H = a.H;
-  // STRIP (E bit 10): the image is a.W = strips x W pixels wide and each band row is one W-px column
-  // strip of an image row, strip rows ordered (image, strip, y) so a band streams down a strip; the
-  // strip's two border columns are real pixels of its neighbours (one extra 1-KB piece per row from
-  // waves 0 / 1, a zero dummy from the others), and with in_up = 2 the pieces gather the nearest
-  // upsample of a half-size input
-  const int strips = STRIP ? a.W / W : 1;
-  const int HS = H * strips;
-  const int T = a.N * HS;  // output rows (strip rows)
-  struct RowG { size_t base; int y, irow, x0; };  // first pixel, y, image row n*H + y, strip x origin
-  auto row_geom = [&](int q) -> RowG {
-    if constexpr (!STRIP) {
-      return RowG{(size_t)q * W, q % H, q, 0};
-    } else {
-      const int nq = q / HS, rem = q - nq * HS, j = rem / H, y = rem - j * H;
-      return RowG{(size_t)(nq * H + y) * a.W + j * W, y, nq * H + y, j * W};
-    }
-  };
-  const int upsh = STRIP && a.in_up == 2 ? 1 : 0;
-  // input offset (bytes, chunk lc) of pixel sx of image row irow (STRIP)
-  auto src_off = [&](int irow, int sx, int lc) -> uint32_t {
-    const size_t px = (size_t)(irow >> upsh) * (a.W >> upsh) + (sx >> upsh);
-    return (uint32_t)((px * a.ldx + a.xcoff + lc * 8) * 2);
-  };
-#ifdef SR_BAND_STAMPS
-  const unsigned long long t_start = __builtin_readcyclecounter();
-  unsigned long long ph[4] = {0ull, 0ull, 0ull, 0ull};  // row wait / barrier / MFMA / epilogue
-#endif
-  const int G = gridDim.x;
-  const int bb = blockIdx.x;
-  const int s0 = (int)((int64_t)bb * T / G), s1 = (int)((int64_t)(bb + 1) * T / G);
-  const __amdgpu_buffer_rsrc_t xr = make_rsrc(a.x, a.x_bytes);
-  const __amdgpu_buffer_rsrc_t wr = make_rsrc(a.w, a.w_bytes);
-  const __amdgpu_buffer_rsrc_t gr = make_rsrc(a.gate, a.g_bytes);
-  const __amdgpu_buffer_rsrc_t rr = make_rsrc(a.res, a.r_bytes);
-  const __amdgpu_buffer_rsrc_t rr2 = make_rsrc(a.res2, a.r2_bytes);
-  const __amdgpu_buffer_rsrc_t dr = make_rsrc(a.dot, a.d_bytes);
-
-  // weights: one coalesced LDS-DMA image [co][tap][ci] (1 KB contiguous per wave instruction),
-  // then each wave reads its MFMA fragments from it: co = wc*32 + 8*(c16>>2) + 4*c + (c16&3)
-  // (DIRECT row permutation), K chunk kk*32 + 8*g of every tap
-  for (int p = w; p < WBYTES / 1024; p += NWV) {
-    const int e = p * 1024 + lane * 16;
-    const int co = e / WROW, off = e - co * WROW;
-    if constexpr (STRIP) {  // Cin may be 8 / 16 / 24 below CIN (the RRDBNet conv_last dgrad): zero-padded per tap
-      const int tap = off / (CIN * 2), cib = off - tap * (CIN * 2);
-      glds16(wr, wimg + p * 1024, cib < a.Cin * 2 ? (uint32_t)(co * a.ldw * 2 + tap * a.Cin * 2 + cib) : SR_OOB);
-    } else {
-      glds16(wr, wimg + p * 1024, (uint32_t)(co * a.ldw * 2 + off));
-    }
-  }
-  const int nn = wc * 32 + 8 * g;  // this lane's 8 output channels
-  float bv[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) bv[j] = 0.f;
-  if (a.bias) {
-    const f32x4 b0 = *(const f32x4*)(a.bias + nn), b1 = *(const f32x4*)(a.bias + nn + 4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { bv[j] = b0[j]; bv[4 + j] = b1[j]; }
-  }
-  float rsv = a.alpha;  // RSC: alpha * row_scale of image s0 / H + lane (a band spans < 64 images)
-  if constexpr (RSC) {
-    const int ni = s0 / H + lane;
-    rsv = ni < a.N ? a.alpha * a.row_scale[ni] : 0.f;
-  }
-  u32x4 bw[9][2][2];
-  auto read_weights = [&]() {
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          const int co = wc * 32 + 8 * (c16 >> 2) + 4 * c + (c16 & 3);
-          bw[tap][kk][c] = kk < KH ? *(const u32x4*)(wimg + co * WROW + (tap * CIN + kk * 32 + 8 * g) * 2)
-                                   : u32x4{0u, 0u, 0u, 0u};
-        }
-    // every fragment in registers (and the compiler knows it) before the ring overwrites the image
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) asm volatile("" ::"v"(bw[tap][kk][c]));
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  };
-  auto zero_borders = [&]() {  // pixel rows 0 and W + 1 of every slot (STRIP: DMA'd per row), and the zero slot S
-    for (int i = tid; i < (STRIP ? 0 : S * 2 * 8); i += NWV * 64) {
-      const int sl = i >> 4, side = (i >> 3) & 1, ch = i & 7;
-      *(u32x4*)(smem + sl * SLOT + (side ? (W + 1) * 128 : 0) + ch * 16) = u32x4{0u, 0u, 0u, 0u};
-    }
-    for (int i = tid; i < SLOT / 16; i += NWV * 64) *(u32x4*)(smem + S * SLOT + i * 16) = u32x4{0u, 0u, 0u, 0u};
-  };
-  if constexpr (!WSEP) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) asm volatile("" ::"v"(bv[j]));
-    asm volatile("" ::"v"(rsv));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    read_weights();
-    __syncthreads();
-    zero_borders();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-  } else {
-    zero_borders();  // disjoint from the weight image and from the pixel rows the prologue DMAs
-  }
-#ifdef SR_BAND_STAMPS
-  const unsigned long long t_loaded = __builtin_readcyclecounter();
-#endif
-
-  // DMA of global row q (pixels 1..W of slot q % S); rows outside [0, T) read zeros
-  const int lc_lane = lane & 7;
-  auto issue_row = [&](int q) {
-    char* slot = smem + (q % S) * SLOT;
-    const bool qv = q >= 0 && q < T;
-    RowG rg{};
-    if constexpr (STRIP) rg = row_geom(q);
-#pragma unroll
-    for (int j = 0; j < PPW; ++j) {
-      const int k = w * PPW + j;            // piece: pixel rows 1 + 8k .. 8 + 8k
-      const int px = 1 + 8 * k + (lane >> 3);
-      const int lc = lc_lane ^ (px & 7);    // logical 16-B chunk landing in physical slot lane & 7
-      const bool v = qv && lc * 8 < a.Cin;
-      uint32_t off;
-      if constexpr (STRIP) off = src_off(rg.irow, rg.x0 + px - 1, lc);
-      else off = (uint32_t)((((size_t)q * W + (px - 1)) * a.ldx + a.xcoff + lc * 8) * 2);
-      glds16(xr, slot + (1 + 8 * k) * 128, v ? off : SR_OOB);
-    }
-    if constexpr (STRIP) {
-      // wave 0: slot pixels 0..7 (the left border, 1..7 again as piece 0 has them), wave 1: W-6..W+1
-      // (W+1 the right border): a rewrite of the same bytes is harmless.  The image's outer columns
-      // load as zeros (OOB).  Other waves: one zero dummy into the zero slot (uniform vmcnt counts).
-      if (w < 2) {
-        const int pb = w == 0 ? 0 : W - 6;
-        const int px = pb + (lane >> 3);
-        const int lc = lc_lane ^ (px & 7);
-        const int sx = rg.x0 + px - 1;
-        const bool v = qv && (unsigned)sx < (unsigned)a.W && lc * 8 < a.Cin;
-        glds16(xr, slot + pb * 128, v ? src_off(rg.irow, sx, lc) : SR_OOB);
-      } else {
-        glds16(xr, smem + S * SLOT, SR_OOB);
-      }
-    }
-  };
-  const bool gok = GATE != 3 || (nn >= a.gcol0 && nn < a.gcol1);
-  const bool rok = nn < a.rcols;
-  auto unpack8 = [](const u32x4& q, float* o) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      o[2 * j] = bf16_to_f32(q[j] & 0xffff);
-      o[2 * j + 1] = bf16_to_f32(q[j] >> 16);
-    }
-  };
-  char* epi = smem + (S + 1) * SLOT + w * EPI;
-  // gate / res / res2 of this wave's pixels of output row q into its staging buffer (NG ops)
-  auto issue_staging = [&](int q) {
-    const bool qv = q < T;
-    const size_t mb = row_geom(q).base;
-#pragma unroll
-    for (int i = 0; i < PT; ++i) {
-      const size_t m = mb + wp * PT * 16 + i * 16 + c16;
-      if constexpr (GATE != 0)
-        glds16(gr, epi + i * 1024, qv && gok ? (uint32_t)((m * a.ldg + a.gcoff + nn) * 2) : SR_OOB);
-      if constexpr (RES)
-        glds16(rr, epi + (IR * PT + i) * 1024, qv && rok ? (uint32_t)((m * a.ldr + a.rcoff + nn) * 2) : SR_OOB);
-      if constexpr (RES2)
-        glds16(rr2, epi + (IR2 * PT + i) * 1024, qv && rok ? (uint32_t)((m * a.ldr2 + a.r2coff + nn) * 2) : SR_OOB);
-      if constexpr (DOT)
-        glds16(dr, epi + (ID * PT + i) * 1024, qv ? (uint32_t)((m * a.ldd + a.dcoff + nn) * 2) : SR_OOB);
-    }
-  };
-  // prologue: rows s0 - 1 .. s0 + LA - 1 (s0 - 1 first: the oldest), then row s0's staging
-  if (s0 < s1) {
-    for (int q = s0 - 1; q < s0 + LA; ++q) issue_row(q);
-    issue_staging(s0);
-  }
-  if constexpr (WSEP) {
-    // this wave's weight pieces landed (older than the (LA + 1) * PPW + NG prologue ops just
-    // issued), then every wave's; the zeros visible to every wave
-#pragma unroll
-    for (int j = 0; j < 8; ++j) asm volatile("" ::"v"(bv[j]));
-    asm volatile("" ::"v"(rsv));
-    vm_wait_dyn(s0 < s1 ? (LA + 1) * PPWX + NG : 0);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-    read_weights();
-  }
-  const int n0 = s0 / H;
-  float cst[8];  // band-reduced channel sums (a.cs_band)
-#pragma unroll
-  for (int j = 0; j < 8; ++j) cst[j] = 0.f;
-
-  // Per row, in issue order: [MFMAs] [epilogue] [staging of row s + 1: NG] [pieces of row
-  // s + LA: PPW] [stores: PT + NC].  Vector memory ops complete in issue order, so a wait for
-  // one op is a wait for every older one: the row pieces and the staging are issued after the
-  // epilogue, so neither wait below ever covers the stores or the DMA of the row just issued.
-#pragma unroll 1
-  for (int s = s0; s < s1; ++s) {
-#ifdef SR_BAND_STAMPS
-    const unsigned long long t0 = __builtin_readcyclecounter();
-#endif
-    // rows <= s + 1 landed: the ops issued after row s + 1's pieces may stay in flight
-    if (s + 1 >= s0 + LA) {
-      constexpr int STEADY = (PT + NC) + (LA - 2) * KROW;
-      static_assert(STEADY <= 63, "band: too many vector memory ops in flight for vmcnt");
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(STEADY) : "memory");
-    } else {
-      vm_wait_dyn((s0 + LA - 2 - s) * PPWX + NG + (s - s0) * KROW);
-    }
-#ifdef SR_BAND_STAMPS
-    const unsigned long long t1 = __builtin_readcyclecounter();
-#endif
-    // every wave's pieces of row s + 1 are in LDS, and every wave is done with row s - 2,
-    // whose slot row s + LA reuses (S = LA + 2)
-    pp_barrier();
-#ifdef SR_BAND_STAMPS
-    const unsigned long long t2 = __builtin_readcyclecounter();
-#endif
-    const RowG rgs = row_geom(s);
-    const int n_img = STRIP ? 0 : s / H, y = rgs.y;
-
-    f32x4 acc[PT][2];
-#pragma unroll
-    for (int i = 0; i < PT; ++i)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) acc[i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int sl1 = s % S;
-    const int sl0 = y == 0 ? S : (sl1 == 0 ? S - 1 : sl1 - 1);      // zero slot above an image
-    const int sl2 = y == H - 1 ? S : (sl1 == S - 1 ? 0 : sl1 + 1);  // ... and below it
-    const char* srows[3] = {smem + sl0 * SLOT, smem + sl1 * SLOT, smem + sl2 * SLOT};
-    // K steps (tap, K half) in order.  Fragment reads run FD - 1 K steps ahead of the MFMAs.  They
-    // are inline-asm ds_reads with hand-counted lgkmcnt waits that pass the fragments through (so
-    // no MFMA can be scheduled before its wait): the compiler otherwise sinks every read to just
-    // before its use and exposes the full LDS latency per 2 MFMAs (one wave per SIMD has nothing
-    // else to run).
-    constexpr int NK = 9 * KH;
-    constexpr int FD = PT >= 8 ? 2 : 5;  // 8 pixel tiles (CO 256 over 8 waves): 2 K steps of fragments
-    u32x4 fa[FD][PT];
-    uint32_t rbase[3];
-#pragma unroll
-    for (int ty = 0; ty < 3; ++ty)
-      rbase[ty] = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)srows[ty];
-    auto read_k = [&](int k, u32x4 (&dst)[PT]) {
-      const int tap = k / KH, kk = k % KH, ty = tap / 3, tx = tap % 3;
-#pragma unroll
-      for (int i = 0; i < PT; ++i) {
-        const uint32_t ad = rbase[ty] + swz128(wp * PT * 16 + i * 16 + c16 + tx, kk * 4 + g);
-        asm volatile("ds_read_b128 %0, %1" : "=v"(dst[i]) : "v"(ad));
-      }
-    };
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int k = 0; k < FD - 1; ++k) read_k(k, fa[k]);
-#pragma unroll
-    for (int k = 0; k < NK; ++k) {
-      if (k + FD - 1 < NK) read_k(k + FD - 1, fa[(k + FD - 1) % FD]);
-      const int ahead = (NK - 1 - k < FD - 1 ? NK - 1 - k : FD - 1) * PT;  // reads issued after step k's
-      u32x4* f = fa[k % FD];
-      if constexpr (PT == 1) {
-        switch (ahead) {
-          case 0: asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0])); break;
-          case 1: asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(f[0])); break;
-          case 2: asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(f[0])); break;
-          case 3: asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(f[0])); break;
-          default: asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(f[0])); break;
-        }
-      } else if constexpr (PT == 2) {
-        switch (ahead) {
-          case 0: asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1])); break;
-          case 2: asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(f[0]), "+v"(f[1])); break;
-          case 4: asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(f[0]), "+v"(f[1])); break;
-          case 6: asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(f[0]), "+v"(f[1])); break;
-          default: asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(f[0]), "+v"(f[1])); break;
-        }
-      } else if constexpr (PT == 8) {
-        if (ahead == 0)
-          asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]),
-                       "+v"(f[6]), "+v"(f[7]));
-        else
-          asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]),
-                       "+v"(f[6]), "+v"(f[7]));
-      } else {
-        switch (ahead) {
-          case 0: asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3])); break;
-          case 4: asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3])); break;
-          case 8: asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3])); break;
-          case 12: asm volatile("s_waitcnt lgkmcnt(12)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3])); break;
-          default: asm volatile("s_waitcnt lgkmcnt(15)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3])); break;
-        }
-      }
-      const int tap = k / KH, kk = k % KH;
-#pragma unroll
-      for (int i = 0; i < PT; ++i)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) mfma_chunk<bf16_t>(bw[tap][kk][c], f[i], acc[i][c]);
-    }
-    // The compiler interleaves the epilogue's accumulator reads with the last MFMAs and, on a
-    // branchy path, once left too few wait states between the final MFMA and the read of its
-    // result (acc[PT-1][1][3] came out stale).  Fence the MFMA block and pad it.
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-#ifdef SR_BAND_STAMPS
-    const unsigned long long t3 = __builtin_readcyclecounter();
-#endif
-
-    // this row's staging landed (issued before row s + LA - 1's pieces and row s - 1's stores)
-    if constexpr (NG > 0) {
-      if (s == s0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPWX + PT + NC) : "memory");
-    }
-    float rs = a.alpha;
-    if constexpr (RSC) rs = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rsv), n_img - n0));
-    float cs[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) cs[j] = 0.f;
-    u32x4 ov[PT], avx[PT];
-#pragma unroll
-    for (int i = 0; i < PT; ++i) {
-      float v[8];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { v[r] = acc[i][0][r] + bv[r]; v[4 + r] = acc[i][1][r] + bv[4 + r]; }
-      if constexpr (AUX) {  // activation side output (act_aux_n: GELU' for GELU)
-        float ax[8];
-        act_aux_n(v, ax, ACT, a.slope);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) avx[i][j] = pack_bf16x2(ax[2 * j], ax[2 * j + 1]);
-      } else if constexpr (ACT == 1) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = v[j] > 0.f ? v[j] : 0.f;
-      } else if constexpr (ACT == 2) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = v[j] > 0.f ? v[j] : v[j] * a.slope;
-      } else if constexpr (ACT == 3) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = gelu_exact(v[j]);
-      }
-      float gf[8];
-      if constexpr (GATE != 0) unpack8(*(const u32x4*)(epi + i * 1024 + lane * 16), gf);
-      if constexpr (GATE == 1) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] *= gf[j] > 0.f ? 1.f : a.gate_slope;
-      } else if constexpr (GATE == 2) {  // the stored GELU'
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] *= gf[j];
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] *= rs;
-      if constexpr (RES) {
-        float rf[8];
-        unpack8(*(const u32x4*)(epi + (IR * PT + i) * 1024 + lane * 16), rf);
-        if (rok) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = a.beta * rf[j] + v[j];
-        }
-      }
-      if constexpr (RES2) {
-        float rf[8];
-        unpack8(*(const u32x4*)(epi + (IR2 * PT + i) * 1024 + lane * 16), rf);
-        if (rok) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = a.beta2 * rf[j] + v[j];
-        }
-      }
-      if constexpr (GATE == 3) {
-        if (gok) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] *= gf[j] > 0.f ? 1.f : a.gate_slope;
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) ov[i][j] = pack_bf16x2(v[2 * j], v[2 * j + 1]);
-      if constexpr (CS && DOT) {  // y as stored times the dot operand
-        float df[8];
-        unpack8(*(const u32x4*)(epi + (ID * PT + i) * 1024 + lane * 16), df);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          cs[2 * j] += bf16_to_f32(ov[i][j] & 0xffff) * df[2 * j];
-          cs[2 * j + 1] += bf16_to_f32(ov[i][j] >> 16) * df[2 * j + 1];
-        }
-      } else if constexpr (CS) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          cs[2 * j] += bf16_to_f32(ov[i][j] & 0xffff);
-          cs[2 * j + 1] += bf16_to_f32(ov[i][j] >> 16);
-        }
-      }
-    }
-    if constexpr (NG > 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // staging read before refill
-    issue_staging(s + 1);
-    issue_row(s + LA);
-#pragma unroll
-    for (int i = 0; i < PT; ++i) {
-      const size_t m = rgs.base + wp * PT * 16 + i * 16 + c16;
-      *(u32x4*)((bf16_t*)a.y + m * a.ldy + a.ycoff + nn) = ov[i];
-    }
-    if constexpr (AUX) {
-#pragma unroll
-      for (int i = 0; i < PT; ++i) {
-        const size_t m = rgs.base + wp * PT * 16 + i * 16 + c16;
-        *(u32x4*)((bf16_t*)a.aux + m * a.ldy + a.ycoff + nn) = avx[i];
-      }
-    }
-    if constexpr (CS) {
-      // the 16 lanes of a g group hold the same 8 channels: fixed-order butterfly, then lane
-      // c16 == 0 writes partial row s * WP + wp (P = H * WP rows per image) -- or, band-reduced
-      // (a.cs_band: every band is a.cs_band rows of one image), the running sum over the band's rows
-      // so far to partial row bb * WP + wp, so the last row's store leaves the band's sum
-      // (P = H / cs_band * WP rows per image; same-address stores of one wave land in order)
-      // Band-reduced: each lane keeps its own sums over the band's rows and the butterfly runs once, at
-      // the band's last row (it costs ~1300 cycles per row at one wave per SIMD: 32 cross-lane moves in
-      // 4 dependent rounds); the rows before store the lane's unreduced running sum to the same
-      // address, which the last row's store overwrites (the two stores per row keep the vmcnt counts)
-      if (a.cs_band) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { cst[j] += cs[j]; cs[j] = cst[j]; }
-        if (s + 1 == s1) {
-#pragma unroll
-          for (int off = 1; off < 16; off <<= 1)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) cs[j] += __shfl_xor(cs[j], off, 64);
-        }
-      } else {
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1)
-#pragma unroll
-          for (int j = 0; j < 8; ++j) cs[j] += __shfl_xor(cs[j], off, 64);
-      }
-      float* dstp = a.colsum + ((size_t)(a.cs_band ? bb : s) * WP + wp) * a.Cout + nn;
-      // exactly two vector store instructions per wave (lanes masked): counted in NC
-      if (c16 == 0) *(f32x4*)dstp = f32x4{cs[0], cs[1], cs[2], cs[3]};
-      if (c16 == 0) *(f32x4*)(dstp + 4) = f32x4{cs[4], cs[5], cs[6], cs[7]};
-    }
-#ifdef SR_BAND_STAMPS
-    const unsigned long long t4 = __builtin_readcyclecounter();
-    ph[0] += t1 - t0; ph[1] += t2 - t1; ph[2] += t3 - t2; ph[3] += t4 - t3;
-#endif
-  }
-#ifdef SR_BAND_STAMPS
-  if (a.stamps && tid == 0) {
-    unsigned long long* st = a.stamps + (size_t)blockIdx.x * 16;
-    st[0] = t_start; st[1] = t_loaded; st[2] = __builtin_readcyclecounter(); st[3] = s1 - s0;
-    st[4] = ph[0]; st[5] = ph[1]; st[6] = ph[2]; st[7] = ph[3];
-  }
-#endif
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trailing row pieces (zeros past T) land before exit
-}
-
-// ------------------------------------------------------------------------------------
 // HR tail convs (conv_last: Cout <= 16, NCHW fp32 store, W >= 256, Cin 64..256): row streaming
 // over 32-px column strips.  A block owns (image, strip, band of RB rows); per output row ONE new
 // input row (34 px x Cin, per 64-ch chunk a [40 px][128 B] swizzled image) is DMA'd into a ring
@@ -2991,31 +1604,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_fwd_tail_kernel(FwdArgs a) {
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trailing row pieces land before exit
 }
-
-// ------------------------------------------------------------------------------------
-// Weight gradient.  GEMM per tap: C[co][ci] = sum_p dy[p][co] * x[p + tap][ci] over a
-// K-range of pixels (split-K).  LDS images are [pixels][cols] (rows = K); MFMA operands
-// need 8 consecutive K per lane, read with ds_read_b64_tr_b16 (bf16) or ds_read_b32
-// (f32).  Partial tiles go to an fp32 slab ws[split][tap][co][ci]; blocks of the centre
-// tap and first ci tile also emit the bias-gradient partial sums.
-// ------------------------------------------------------------------------------------
-struct WgArgs {
-  const void* dy;
-  const void* x;
-  float* ws;    // [S][9][Cout][Cin]
-  float* wsb;   // [S][Cout]
-  uint32_t dy_bytes, x_bytes;
-  int N, H, W, M;
-  int Cin, ldx, xcoff;
-  int Cout, ldy, ycoff, out_ps;
-  int in_up;  // nearest upsample factor of the x gather (1 = none)
-  int taps, tap0;  // 9 / 0 for 3x3, 1 / 4 for 1x1 (linear)
-  int tiles_co, tiles_ci, splits, kper;  // kper: pixels per split (multiple of KSTEP)
-  int bias_group;  // pp kernel: > 0 = the bias-role blocks come after all tile blocks, each doing this many splits
-  int bias_fused;  // pp kernel: no bias-role blocks; the centre-tap, first-ci-tile blocks sum dy as well
-  FastDiv fd_W, fd_H, fd_cps;
-  unsigned long long* stamps;  // diagnostics (SR_BAND_STAMPS builds): per-block phase cycles
-};
 
 // 32-byte-block XOR swizzle for the [K rows][256 B] tr-read image (tools/lds_banks.py):
 // the 8 rows a 32-lane half reads ({0..3, 8..11} + base) land on 8 distinct blocks.
@@ -3789,171 +2377,6 @@ __global__ __launch_bounds__(512) void conv3x3_wgrad_pp_kernel(WgArgs a) {
       const int co = co0 + h * 128 + row, ci = ci0 + c4;
       if (co < a.Cout && ci < a.Cin)
         *(f32x4*)(ws + (size_t)co * a.Cin + ci) = *(const f32x4*)(Cs + row * CSTR + c4);
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------
-// Weight gradient of a 1x1 conv (the SwinIR linears: dW[co][ci] = sum_t dy[t][co] x[t][ci] over
-// the tokens t, db[co] = sum_t dy[t][co]), bf16.  A block owns a 192 (co) x 192 (ci) tile over a
-// token K-range (split-K): SwinIR-M's 576 / 184 / 360 / 192 channel counts are 3 / 1 / 2 / 1 such
-// tiles (4-7 % padding, against 28-50 % in 256x256 tiles).  A 64-token K-step is six [64 tok][64 ch]
-// LDS images (128-B rows; 32-B blocks XOR-swizzled by row bits 1 and 3, so the 8 rows a 32-lane
-// half reads with ds_read_b64_tr_b16 land on 8 distinct bank groups): dy co sub-tiles 0-2, then x ci
-// sub-tiles 0-2, DMA'd straight to LDS (wave w: rows 8w .. 8w + 7 of each, the swizzle applied to
-// the lane's source channels).  Three stages, two steps in flight, one barrier per step.  8 waves
-// (2 co x 4 ci), each 96 co x 48 ci (6 x 3 accumulator tiles).  Blocks of the first ci tile also
-// sum dy against a ones operand for the bias (wave (wr, wc): co fragments wc and wc + 4).  Output:
-// the pp kernel's fp32 slab ws[split][Cout][Cin] and bias slab (same reduce).
-// ------------------------------------------------------------------------------------
-SR_DEV uint32_t swz_tr128(uint32_t row, uint32_t byte_in_row) {
-  const uint32_t g = ((row >> 1) & 1u) | (((row >> 3) & 1u) << 1);
-  return row * 128u + ((((byte_in_row >> 5) ^ g) & 3u) << 5) + (byte_in_row & 31u);
-}
-
-__global__ __launch_bounds__(512) void linear_wgrad_kernel(WgArgs a) {
-  constexpr int IMG = 8192;       // [64 tok][64 ch] bf16
-  constexpr int STAGE = 6 * IMG;  // 48 KB
-  constexpr int NST = 3;
-  __shared__ __attribute__((aligned(16))) char smem[NST * STAGE];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = w >> 2, wc = w & 3;
-  const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
-  const int ntile = a.tiles_co * a.tiles_ci;
-  const int split = (int)b / ntile;
-  const int rem = (int)b - split * ntile;
-  const int cot = rem / a.tiles_ci, cit = rem - cot * a.tiles_ci;
-  const int co0 = cot * 192, ci0 = cit * 192;
-  const int p_begin = split * a.kper;
-  const int p_end = min(a.M, p_begin + a.kper);
-  const int nk = (p_end - p_begin + 63) / 64;
-  const __amdgpu_buffer_rsrc_t dyr = make_rsrc(a.dy, a.dy_bytes);
-  const __amdgpu_buffer_rsrc_t xr = make_rsrc(a.x, a.x_bytes);
-
-  // DMA lane geometry: image row drow, physical 16-B slot lane & 7 = logical 32-B block
-  // ((lane & 7) >> 1) ^ g(drow), half lane & 1
-  const int drow = 8 * w + (lane >> 3);
-  const int gsw = ((drow >> 1) & 1) | (((drow >> 3) & 1) << 1);
-  const int lch = ((((lane & 7) >> 1) ^ gsw) << 4) + (lane & 1) * 8;
-  uint32_t offy[3], offx[3];
-  bool vy[3], vx[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const int co = co0 + i * 64 + lch, ci = ci0 + i * 64 + lch;
-    vy[i] = co < a.Cout;
-    vx[i] = ci < a.Cin;
-    offy[i] = (uint32_t)((drow * a.ldy + a.ycoff + co) * 2);
-    offx[i] = (uint32_t)((drow * a.ldx + a.xcoff + ci) * 2);
-  }
-  auto issue = [&](int ks, int stg) {
-    const int p0 = p_begin + ks * 64;
-    char* st = smem + stg * STAGE + w * 1024;
-    const bool tv = p0 + drow < p_end;
-    const uint32_t by = (uint32_t)p0 * (uint32_t)a.ldy * 2u, bx = (uint32_t)p0 * (uint32_t)a.ldx * 2u;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) glds16(dyr, st + i * IMG, tv && vy[i] ? by + offy[i] : SR_OOB);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) glds16(xr, st + (3 + i) * IMG, tv && vx[i] ? bx + offx[i] : SR_OOB);
-  };
-
-  const int tg = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
-  auto tr8 = [&](const char* img, int r0, int col) -> s16x8 {
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) s16x4*)(img + swz_tr128(r0, col * 2)));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) s16x4*)(img + swz_tr128(r0 + 4, col * 2)));
-    return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  };
-  f32x4 acc[6][3];
-#pragma unroll
-  for (int i = 0; i < 6; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  f32x4 accb[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-  const bool bias_here = a.wsb != nullptr && cit == 0;
-  const s16x8 ones = {0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};
-
-  auto compute = [&](int stg) {
-    const char* st = smem + stg * STAGE;
-    s16x8 fa[2][6], fb[2][3];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int r0 = kk * 32 + 8 * tg + tq;
-#pragma unroll
-      for (int i = 0; i < 6; ++i) {
-        const int c = wr * 96 + i * 16;
-        fa[kk][i] = tr8(st + (c >> 6) * IMG, r0, (c & 63) + 4 * tp);
-      }
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const int c = wc * 48 + j * 16;
-        fb[kk][j] = tr8(st + (3 + (c >> 6)) * IMG, r0, (c & 63) + 4 * tp);
-      }
-    }
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kk][i], fb[kk][j], acc[i][j], 0, 0, 0);
-      if (bias_here) {
-        // co fragments wc and wc + 4 of this wave's row block (wave-uniform branches: no indexed
-        // fragment array, which would go to scratch)
-        if (wc == 0) {
-          accb[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kk][0], ones, accb[0], 0, 0, 0);
-          accb[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kk][4], ones, accb[1], 0, 0, 0);
-        } else if (wc == 1) {
-          accb[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kk][1], ones, accb[0], 0, 0, 0);
-          accb[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kk][5], ones, accb[1], 0, 0, 0);
-        } else if (wc == 2) {
-          accb[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kk][2], ones, accb[0], 0, 0, 0);
-        } else {
-          accb[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[kk][3], ones, accb[0], 0, 0, 0);
-        }
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
-  };
-
-  if (nk > 0) issue(0, 0);
-  if (nk > 1) issue(1, 1);
-  int stg = 0;
-  for (int t = 0; t < nk; ++t) {
-    if (t + 1 < nk)
-      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    pp_barrier();  // step t landed for every wave; every wave finished reading step t - 1's stage
-    if (t + 2 < nk) issue(t + 2, stg == 0 ? 2 : stg - 1);
-    compute(stg);
-    stg = stg == 2 ? 0 : stg + 1;
-  }
-
-  float* ws = a.ws + (size_t)split * a.Cout * a.Cin;
-#pragma unroll
-  for (int i = 0; i < 6; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int co = co0 + wr * 96 + i * 16 + (lane >> 4) * 4 + r;
-        const int ci = ci0 + wc * 48 + j * 16 + (lane & 15);
-        if (co < a.Cout && ci < a.Cin) ws[(size_t)co * a.Cin + ci] = acc[i][j][r];
-      }
-  if (bias_here && (lane & 15) == 0) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int i = k == 0 ? wc : wc + 4;
-      if (i < 6) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int co = co0 + wr * 96 + i * 16 + (lane >> 4) * 4 + r;
-          if (co < a.Cout) a.wsb[(size_t)split * a.Cout + co] = accb[k][r];
-        }
-      }
     }
   }
 }
@@ -4993,6 +3416,17 @@ __global__ __launch_bounds__(256) void prep_batch_kernel(const sr_prep_item* __r
   }
 }
 
+}  // namespace
+
+namespace sr_conv __attribute__((visibility("hidden"))) {
+namespace {
+// set by sr_conv3x3_set_variant (tests / A-B timing): an sr_conv_variant of include/sr_hip.h
+int g_variant = SR_VARIANT_AUTO;
+}  // namespace
+bool variant_is(int v) { return g_variant == v; }
+// SR_VARIANT_TILE_ONLY: never a 256x256 kernel (nor any of the narrow-conv families)
+bool tile_only() { return variant_is(SR_VARIANT_TILE_ONLY); }
+
 template <typename T, int BM, int BN, int WM, int WN>
 hipError_t launch_fwd(const FwdArgs& a0, hipStream_t s) {
   FwdArgs a = a0;
@@ -5001,6 +3435,20 @@ hipError_t launch_fwd(const FwdArgs& a0, hipStream_t s) {
   a.tiles = tm * a.tiles_n;
   hipLaunchKernelGGL((conv3x3_fwd_kernel<T, BM, BN, WM, WN>), dim3(a.tiles), dim3(256), 0, s, a);
   return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_fwd_tile_t(const FwdArgs& a, FwdKind k, hipStream_t s) {
+  switch (k) {
+case FK_256_16: return launch_fwd<T, 256, 16, 4, 1>(a, s);
+case FK_256_32: return launch_fwd<T, 256, 32, 4, 1>(a, s);
+case FK_128_64: return launch_fwd<T, 128, 64, 2, 2>(a, s);
+default: return launch_fwd<T, 128, 128, 2, 2>(a, s);
+  }
+}
+
+hipError_t launch_fwd_tile(const FwdArgs& a, FwdKind k, bool bf16, hipStream_t s) {
+  return bf16 ? launch_fwd_tile_t<bf16_t>(a, k, s) : launch_fwd_tile_t<float>(a, k, s);
 }
 
 // pph over 64-px column strips (STRIP): bf16, W a multiple of 64 above 128 (EDSR at LR 256: the body
@@ -5105,9 +3553,6 @@ hipError_t launch_fwd_halo(const FwdArgs& a0, hipStream_t s) {
   return hipGetLastError();
 }
 
-// Kernel family sr_conv3x3_fwd launches for a call (dispatch, kernel names and the
-// epilogue geometry behind colsum all follow this one choice).
-enum FwdKind { FK_HALO, FK_BIG, FK_256_16, FK_256_32, FK_128_64, FK_128_128, FK_LIN, FK_BAND, FK_TAIL, FK_BANDS };
 // the bits of a compile-time epilogue code that the band and lin kernels share (EPI_*)
 int epi_common(const FwdArgs& a) {
   int gate = 0;
@@ -5264,126 +3709,24 @@ int band_cs_rows(const FwdArgs& a) {
 int band_nwv(const FwdArgs& a) {
   return a.W == 128 && !(a.Cout == 32 && (a.colsum || a.dot)) ? 8 : 4;
 }
-// the whole-row forms on NWV waves per block (band_nwv)
-template <int NWV>
-hipError_t launch_band_rows(const FwdArgs& a, hipStream_t s) {
-  FwdArgs ab = a;
-  ab.stamps = g_sr_stamps;
-  ab.cs_band = a.colsum ? band_cs_rows(a) : 0;
-  const dim3 grid(band_grid(a.N * a.H)), blk(NWV * 64);
-  const int e = band_epi(a, grid.x);
-  if (e == 656) {  // instantiated for the RCAN shapes only
-    if (a.W == 64) hipLaunchKernelGGL((conv3x3_fwd_band_kernel<64, 64, 5, 2, 656>), grid, dim3(256), 0, s, ab);
-    else hipLaunchKernelGGL((conv3x3_fwd_band_kernel<64, 128, 3, 2, 656, NWV>), grid, blk, 0, s, ab);
-    return hipGetLastError();
-  }
-#define SR_BAND_E(CO_, W_, LA_, KH_, E_) \
-  case E_: hipLaunchKernelGGL((conv3x3_fwd_band_kernel<CO_, W_, LA_, KH_, E_, NWV>), grid, blk, 0, s, ab); break;
-#define SR_BAND(CO_, W_, LA_, KH_) \
-  if (a.Cout == CO_ && a.W == W_ && a.Cin == 32 * KH_) { \
-switch (e) { \
-  SR_BAND_E(CO_, W_, LA_, KH_, 0) SR_BAND_E(CO_, W_, LA_, KH_, 1) SR_BAND_E(CO_, W_, LA_, KH_, 2) \
-  SR_BAND_E(CO_, W_, LA_, KH_, 4) SR_BAND_E(CO_, W_, LA_, KH_, 16) SR_BAND_E(CO_, W_, LA_, KH_, 20) \
-  SR_BAND_E(CO_, W_, LA_, KH_, 28) \
-  SR_BAND_E(CO_, W_, LA_, KH_, 48) SR_BAND_E(CO_, W_, LA_, KH_, 72) SR_BAND_E(CO_, W_, LA_, KH_, 128) \
-  SR_BAND_E(CO_, W_, LA_, KH_, 304) \
-  default: return hipErrorInvalidValue; \
-} \
-return hipGetLastError(); \
-  }
-  if constexpr (NWV == 4) {  // W 64: one pixel tile per wave
-    SR_BAND(64, 64, 5, 2) SR_BAND(64, 64, 5, 1) SR_BAND(32, 64, 5, 2) SR_BAND(32, 64, 5, 1)
-  }
-  SR_BAND(64, 128, 3, 2) SR_BAND(64, 128, 3, 1) SR_BAND(32, 128, 4, 2) SR_BAND(32, 128, 4, 1)
-#undef SR_BAND
-#undef SR_BAND_E
-  return hipErrorInvalidValue;
-}
-hipError_t launch_band_strip(const FwdArgs& a, hipStream_t s) {
-  const int rows = a.N * a.H * (a.W / 128);
-  FwdArgs ab = a;
-  ab.stamps = g_sr_stamps;
-  const dim3 grid(band_grid(rows));
-  if (a.Cin <= 32 && a.Cout > 64) {  // plain epilogue only (fwd_use_band_strip)
-    if (a.Cout == 256) hipLaunchKernelGGL((conv3x3_fwd_band_kernel<256, 128, 3, 1, 1024, 8>), grid, dim3(512), 0, s, ab);
-    else hipLaunchKernelGGL((conv3x3_fwd_band_kernel<128, 128, 3, 1, 1024, 8>), grid, dim3(512), 0, s, ab);
-    return hipGetLastError();
-  }
-  if (a.Cin <= 32) {
-    switch (band_epi(a, grid.x)) {
-      case 0: hipLaunchKernelGGL((conv3x3_fwd_band_kernel<64, 128, 3, 1, 1024, 8>), grid, dim3(512), 0, s, ab); break;
-      case 4: hipLaunchKernelGGL((conv3x3_fwd_band_kernel<64, 128, 3, 1, 1028, 8>), grid, dim3(512), 0, s, ab); break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  switch (band_epi(a, grid.x)) {
-    case 0: hipLaunchKernelGGL((conv3x3_fwd_band_kernel<64, 128, 3, 2, 1024, 8>), grid, dim3(512), 0, s, ab); break;
-    case 1: hipLaunchKernelGGL((conv3x3_fwd_band_kernel<64, 128, 3, 2, 1025, 8>), grid, dim3(512), 0, s, ab); break;
-    case 2: hipLaunchKernelGGL((conv3x3_fwd_band_kernel<64, 128, 3, 2, 1026, 8>), grid, dim3(512), 0, s, ab); break;
-    case 4: hipLaunchKernelGGL((conv3x3_fwd_band_kernel<64, 128, 3, 2, 1028, 8>), grid, dim3(512), 0, s, ab); break;
-    default: return hipErrorInvalidValue;
+
+hipError_t launch_fwd_tail(const FwdArgs& a, hipStream_t s) {
+  FwdArgs b = a;
+  b.tiles = a.H < 32 ? a.H : 32;  // rows per band
+  const dim3 grid((unsigned)(a.N * (a.W / 32) * ((a.H + b.tiles - 1) / b.tiles)));
+  switch (a.Cin / 64) {
+    case 1: hipLaunchKernelGGL(conv3x3_fwd_tail_kernel<1>, grid, dim3(256), 0, s, b); break;
+    case 2: hipLaunchKernelGGL(conv3x3_fwd_tail_kernel<2>, grid, dim3(256), 0, s, b); break;
+    case 3: return hipErrorInvalidValue;
+    default: hipLaunchKernelGGL(conv3x3_fwd_tail_kernel<4>, grid, dim3(256), 0, s, b); break;
   }
   return hipGetLastError();
-}
-hipError_t launch_band(const FwdArgs& a, hipStream_t s) {
-  if (a.W > 128 || a.in_up != 1) return launch_band_strip(a, s);
-  return band_nwv(a) == 8 ? launch_band_rows<8>(a, s) : launch_band_rows<4>(a, s);
 }
 
-template <typename T>
-hipError_t dispatch_fwd(const FwdArgs& a, hipStream_t s) {
-  switch (fwd_kind(a, sizeof(T) == 2)) {
-case FK_LIN: {
-  FwdArgs b = a;
-  const int e = lin_epi(a);
-  if (lin_use_wk(a)) {  // 128-token x 192-channel tiles, K streamed
-    const dim3 grid(((a.M + 127) / 128) * ((a.Cout + 191) / 192));
-    if (e == 0) hipLaunchKernelGGL(linear_wk_kernel<0>, grid, dim3(256), 0, s, b);
-    else if (e == 8) hipLaunchKernelGGL(linear_wk_kernel<8>, grid, dim3(256), 0, s, b);
-    else if (e == 67) hipLaunchKernelGGL(linear_wk_kernel<67>, grid, dim3(256), 0, s, b);
-    else if (e == 16) hipLaunchKernelGGL(linear_wk_kernel<16>, grid, dim3(256), 0, s, b);
-    else hipLaunchKernelGGL(linear_wk_kernel<144>, grid, dim3(256), 0, s, b);
-    return hipGetLastError();
-  }
-  if (a.Cin > 192) {  // wide K: 64-token tiles, the whole K (<= 384 / 576) staged
-    b.tiles = (a.M + 63) / 64;
-#define SR_LINW_E(CG_, NP_, E_) \
-  case E_: hipLaunchKernelGGL((conv3x3_lin_kernel<64, CG_, NP_, E_>), dim3(b.tiles), dim3(256), 0, s, b); break;
-#define SR_LINW(CG_, NP_) \
-  case NP_: \
-switch (e) { \
-  SR_LINW_E(CG_, NP_, 0) SR_LINW_E(CG_, NP_, 16) SR_LINW_E(CG_, NP_, 144) \
-  default: hipLaunchKernelGGL((conv3x3_lin_kernel<64, CG_, NP_, -1>), dim3(b.tiles), dim3(256), 0, s, b); \
-} \
-break;
-    if (a.Cin <= 384) {
-      switch ((a.Cout + 127) / 128) { SR_LINW(6, 1) SR_LINW(6, 2) SR_LINW(6, 3) default: return hipErrorInvalidValue; }
-    } else {
-      switch ((a.Cout + 127) / 128) { SR_LINW(9, 1) SR_LINW(9, 2) SR_LINW(9, 3) default: return hipErrorInvalidValue; }
-    }
-#undef SR_LINW
-#undef SR_LINW_E
-    return hipGetLastError();
-  }
-  b.tiles = (a.M + 127) / 128;
-#define SR_LIN_E(NP_, E_) \
-  case E_: hipLaunchKernelGGL((conv3x3_lin_kernel<128, 3, NP_, E_>), dim3(b.tiles), dim3(256), 0, s, b); break;
-#define SR_LIN(NP_) \
-  case NP_: \
-switch (e) { \
-  SR_LIN_E(NP_, 0) SR_LIN_E(NP_, 8) SR_LIN_E(NP_, 16) SR_LIN_E(NP_, 67) SR_LIN_E(NP_, 144) \
-  default: hipLaunchKernelGGL((conv3x3_lin_kernel<128, 3, NP_, -1>), dim3(b.tiles), dim3(256), 0, s, b); \
-} \
-break;
-  switch ((a.Cout + 127) / 128) {
-    SR_LIN(1) SR_LIN(2) SR_LIN(3) SR_LIN(4) SR_LIN(5)
-    default: return hipErrorInvalidValue;
-  }
-#undef SR_LIN
-#undef SR_LIN_E
-  return hipGetLastError();
-}
+hipError_t dispatch_fwd(const FwdArgs& a, bool bf, hipStream_t s) {
+  const FwdKind k = fwd_kind(a, bf);
+  switch (k) {
+case FK_LIN: return launch_lin(a, s);
 case FK_BAND: return launch_band(a, s);
 case FK_BANDS: {
   // 64-channel output column slices (the last may be 32 wide), each a band launch with the
@@ -5408,30 +3751,16 @@ case FK_BANDS: {
   }
   return hipSuccess;
 }
-case FK_TAIL: {
-  FwdArgs b = a;
-  b.tiles = a.H < 32 ? a.H : 32;  // rows per band
-  const dim3 grid((unsigned)(a.N * (a.W / 32) * ((a.H + b.tiles - 1) / b.tiles)));
-  switch (a.Cin / 64) {
-    case 1: hipLaunchKernelGGL(conv3x3_fwd_tail_kernel<1>, grid, dim3(256), 0, s, b); break;
-    case 2: hipLaunchKernelGGL(conv3x3_fwd_tail_kernel<2>, grid, dim3(256), 0, s, b); break;
-    case 3: return hipErrorInvalidValue;
-    default: hipLaunchKernelGGL(conv3x3_fwd_tail_kernel<4>, grid, dim3(256), 0, s, b); break;
-  }
-  return hipGetLastError();
-}
+case FK_TAIL: return launch_fwd_tail(a, s);
 case FK_HALO: return launch_fwd_halo(a, s);
 case FK_BIG: return launch_fwd_big(a, s);
-case FK_256_16: return launch_fwd<T, 256, 16, 4, 1>(a, s);
-case FK_256_32: return launch_fwd<T, 256, 32, 4, 1>(a, s);
-case FK_128_64: return launch_fwd<T, 128, 64, 2, 2>(a, s);
-default: return launch_fwd<T, 128, 128, 2, 2>(a, s);
+default: return launch_fwd_tile(a, k, bf, s);
   }
 }
 
 inline int tile_for(int c) { return c <= 16 ? 16 : c <= 32 ? 32 : c <= 64 ? 64 : 128; }
 // wgrad tile (co x ci): grow the larger side until 4 waves each own a 16x16 sub-tile.
-inline void wg_tiles(int cout, int cin, int* bm, int* bn) {
+void wg_tiles(int cout, int cin, int* bm, int* bn) {
   int m = tile_for(cout), n = tile_for(cin);
   while ((m / 16) * (n / 16) < 4) {
     if (m <= n) n *= 2; else m *= 2;
@@ -5468,6 +3797,49 @@ hipError_t dispatch_wg(const WgArgs& a, hipStream_t s) {
   SR_WG(32, 32)
 #undef SR_WG
   return hipErrorInvalidValue;
+}
+
+hipError_t launch_wg_tile(const WgArgs& a, bool bf16, hipStream_t s) {
+  return bf16 ? dispatch_wg<bf16_t>(a, s) : dispatch_wg<float>(a, s);
+}
+
+// The 256 x 256 kernels (wg_use_big).
+hipError_t launch_wg_big(WgArgs a, const sr_conv3x3_wgrad_desc* d, hipStream_t s) {
+  const int S = a.splits, taps = a.taps;
+  a.tiles_co = (a.Cout + 255) / 256;
+  a.tiles_ci = (a.Cin + 255) / 256;
+  a.bias_fused = wg_bias_fused(d) ? 1 : 0;
+  a.bias_group = a.bias_fused ? 0 : wg_bias_group(d);
+  // bias-role blocks per co tile: none (fused into the centre-tap blocks), one per bias_group splits, or one per split
+  const int bias_splits = a.bias_fused || !a.wsb ? 0 : a.bias_group > 0 ? (S + a.bias_group - 1) / a.bias_group : S;
+  const dim3 grid(S * taps * a.tiles_co * a.tiles_ci + bias_splits * a.tiles_co);
+  if (!wg_use_pp(d)) hipLaunchKernelGGL(conv3x3_wgrad_big_kernel, grid, dim3(512), 0, s, a);
+  else if (variant_is(SR_VARIANT_FOUR_PHASE)) hipLaunchKernelGGL(conv3x3_wgrad_pp_kernel<false>, grid, dim3(512), 0, s, a);
+  else hipLaunchKernelGGL(conv3x3_wgrad_pp_kernel<true>, grid, dim3(512), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_wg_ring(WgArgs a, const sr_conv3x3_wgrad_desc* d, hipStream_t s) {
+  const int S = a.splits;
+  a.tiles_co = ring_tiles_co(d);
+  a.tiles_ci = (a.Cin + 63) / 64;
+  const int ct = ring_ct(d);
+  const dim3 grid(S * a.tiles_ci * a.tiles_co);
+  if (ct == 1) hipLaunchKernelGGL(conv3x3_wgrad_ring_kernel<1>, grid, dim3(256), 0, s, a);
+  else if (ct == 2) hipLaunchKernelGGL(conv3x3_wgrad_ring_kernel<2>, grid, dim3(256), 0, s, a);
+  else if (ct == 3) hipLaunchKernelGGL(conv3x3_wgrad_ring_kernel<3>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(conv3x3_wgrad_ring_kernel<4>, grid, dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_wg_row3(WgArgs a, hipStream_t s) {
+  const int S = a.splits;
+  a.tiles_co = a.Cout / 256;
+  a.tiles_ci = a.Cin / 128;
+  a.bias_group = wg_row3_bg();
+  const int nb = S * 3 * a.tiles_co * a.tiles_ci + (a.wsb ? (S + a.bias_group - 1) / a.bias_group * a.tiles_co : 0);
+  hipLaunchKernelGGL(conv3x3_wgrad_row3_kernel, dim3(nb), dim3(256), 0, s, a);
+  return hipGetLastError();
 }
 
 // Weight gradients with >= 128 channels each side that are not multiples of 128 (SwinIR linears
@@ -5700,7 +4072,7 @@ int colsum_parts(const sr_conv3x3_desc* d, const FwdArgs& a0) {
   if (HW % rows) return 0;
   return HW / rows * (nt / 64);
 }
-}  // namespace
+}  // namespace sr_conv
 
 extern "C" {
 
@@ -5748,7 +4120,7 @@ int sr_conv3x3_fwd(const sr_conv3x3_desc* d, const void* x, const void* w, const
   a.r_bytes = res ? (uint32_t)((size_t)M * d->ldr * SZ) : 0;
   a.r2_bytes = res2 ? (uint32_t)((size_t)M * d->ldr2 * SZ) : 0;
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e = d->dtype == SR_BF16 ? dispatch_fwd<bf16_t>(a, s) : dispatch_fwd<float>(a, s);
+  hipError_t e = dispatch_fwd(a, d->dtype == SR_BF16, s);
   return sr_check(e, "conv3x3_fwd launch");
 }
 
@@ -5774,17 +4146,7 @@ int sr_linear_ln_fwd(const sr_conv3x3_desc* d, const void* x, const float* ln_ga
   a.ln_C = ln_C; a.ln_eps = eps;
   a.tiles = (a.M + 127) / 128;
   hipStream_t s = (hipStream_t)stream;
-#define SR_LNL(NP_)                                                                                       \
-  case NP_:                                                                                               \
-    if (e == 0) hipLaunchKernelGGL((conv3x3_lin_kernel<128, 3, NP_, 0, true>), dim3(a.tiles), dim3(256), 0, s, a); \
-    else hipLaunchKernelGGL((conv3x3_lin_kernel<128, 3, NP_, 67, true>), dim3(a.tiles), dim3(256), 0, s, a); \
-    break;
-  switch ((a.Cout + 127) / 128) {
-    SR_LNL(1) SR_LNL(2) SR_LNL(3) SR_LNL(4) SR_LNL(5)
-    default: return sr_fail(SR_EINVAL, "linear_ln_fwd: Cout > 640");
-  }
-#undef SR_LNL
-  return sr_check(hipGetLastError(), "linear_ln_fwd launch");
+  return launch_lin_ln(a, e, s);
 }
 
 // 1 when sr_conv3x3_fwd can fuse the dot partials (d->dot) into this conv with a residual operand:
@@ -5875,7 +4237,7 @@ size_t sr_conv3x3_wgrad_workspace(const sr_conv3x3_wgrad_desc* d) {
 
 }  // extern "C"
 
-namespace {
+namespace sr_conv __attribute__((visibility("hidden"))) {
 // The slab reduce of a sr_conv3x3_wgrad call (S splits of its plan, slab ws, bias slab wsb)
 int wgrad_reduce_launch(const sr_conv3x3_wgrad_desc* d, int S, int taps, const float* ws, const float* wsb, float* dw,
                         float* db, const int* co_map, const int* ci_map, hipStream_t s) {
@@ -5935,7 +4297,7 @@ int wgrad_reduce_launch(const sr_conv3x3_wgrad_desc* d, int S, int taps, const f
   }
   return sr_check(hipGetLastError(), "conv3x3_wgrad reduce launch");
 }
-}  // namespace
+}  // namespace sr_conv
 
 extern "C" {
 
@@ -5978,43 +4340,11 @@ int sr_conv3x3_wgrad(const sr_conv3x3_wgrad_desc* d, const void* dy, const void*
   hipStream_t s = (hipStream_t)stream;
   hipError_t e;
   a.stamps = g_sr_stamps;
-  if (wg_use_halo(d)) {
-    a.tiles_co = ring_tiles_co(d);
-    a.tiles_ci = (a.Cin + 63) / 64;
-    const int ct = ring_ct(d);
-    const dim3 grid(S * a.tiles_ci * a.tiles_co);
-    if (ct == 1) hipLaunchKernelGGL(conv3x3_wgrad_ring_kernel<1>, grid, dim3(256), 0, s, a);
-    else if (ct == 2) hipLaunchKernelGGL(conv3x3_wgrad_ring_kernel<2>, grid, dim3(256), 0, s, a);
-    else if (ct == 3) hipLaunchKernelGGL(conv3x3_wgrad_ring_kernel<3>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(conv3x3_wgrad_ring_kernel<4>, grid, dim3(256), 0, s, a);
-    e = hipGetLastError();
-  } else if (wg_use_lin(d)) {
-    a.tiles_co = (a.Cout + 191) / 192;
-    a.tiles_ci = (a.Cin + 191) / 192;
-    hipLaunchKernelGGL(linear_wgrad_kernel, dim3(S * a.tiles_co * a.tiles_ci), dim3(512), 0, s, a);
-    e = hipGetLastError();
-  } else if (wg_use_row3(d)) {
-    a.tiles_co = a.Cout / 256;
-    a.tiles_ci = a.Cin / 128;
-    a.bias_group = wg_row3_bg();
-    const int nb = S * 3 * a.tiles_co * a.tiles_ci + (a.wsb ? (S + a.bias_group - 1) / a.bias_group * a.tiles_co : 0);
-    hipLaunchKernelGGL(conv3x3_wgrad_row3_kernel, dim3(nb), dim3(256), 0, s, a);
-    e = hipGetLastError();
-  } else if (wg_use_big(d)) {
-    a.tiles_co = (a.Cout + 255) / 256;
-    a.tiles_ci = (a.Cin + 255) / 256;
-    a.bias_fused = wg_bias_fused(d) ? 1 : 0;
-    a.bias_group = a.bias_fused ? 0 : wg_bias_group(d);
-    // bias-role blocks per co tile: none (fused into the centre-tap blocks), one per bias_group splits, or one per split
-    const int bias_splits = a.bias_fused || !a.wsb ? 0 : a.bias_group > 0 ? (S + a.bias_group - 1) / a.bias_group : S;
-    const dim3 grid(S * taps * a.tiles_co * a.tiles_ci + bias_splits * a.tiles_co);
-    if (!wg_use_pp(d)) hipLaunchKernelGGL(conv3x3_wgrad_big_kernel, grid, dim3(512), 0, s, a);
-    else if (variant_is(SR_VARIANT_FOUR_PHASE)) hipLaunchKernelGGL(conv3x3_wgrad_pp_kernel<false>, grid, dim3(512), 0, s, a);
-    else hipLaunchKernelGGL(conv3x3_wgrad_pp_kernel<true>, grid, dim3(512), 0, s, a);
-    e = hipGetLastError();
-  } else {
-    e = d->dtype == SR_BF16 ? dispatch_wg<bf16_t>(a, s) : dispatch_wg<float>(a, s);
-  }
+  if (wg_use_halo(d)) e = launch_wg_ring(a, d, s);
+  else if (wg_use_lin(d)) e = launch_wg_lin(a, s);
+  else if (wg_use_row3(d)) e = launch_wg_row3(a, s);
+  else if (wg_use_big(d)) e = launch_wg_big(a, d, s);
+  else e = launch_wg_tile(a, d->dtype == SR_BF16, s);
   if (e != hipSuccess) return sr_check(e, "conv3x3_wgrad launch");
   if (d->accumulate & 2) return SR_OK;  // bit 1: slab only (sr_conv3x3_wgrad_reduce later, e.g. on another stream)
   return wgrad_reduce_launch(d, S, taps, a.ws, a.wsb, dw, db, co_map, ci_map, s);

@@ -6,7 +6,7 @@
 // backward scatters with atomics and re-reads the columns once per offset channel.
 //
 // Here the deformable part is reduced to two batched HBM-bound passes around MFMA GEMMs
-// (the GEMMs are the 1x1 path of conv3x3.hip):
+// (the GEMMs are the 1x1 path of the conv code: conv3x3.hip selects, conv3x3_linear.hip has the kernels):
 //   sr_dcn_im2col : cols[p][g][tap][ci] = mask * bilinear(x, p + tap + offset), all images
 //                   in one launch, pixel-major rows so the GEMM reads them as a K-contiguous
 //                   operand; x is NHWC so each bilinear corner is a 16-byte channel vector.

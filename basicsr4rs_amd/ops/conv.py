@@ -1,4 +1,5 @@
-"""3x3 convolution ops on NHWC feature maps, backed by libsr_hip (csrc/conv3x3.hip).
+"""3x3 convolution ops on NHWC feature maps, backed by libsr_hip (csrc/conv3x3.hip and
+the kernel family files csrc/conv3x3_*.hip).
 
 These replace the cuDNN ``nn.Conv2d(C, C', 3, 1, 1)`` calls of the reference SR nets
 (basicsr/archs/arch_util.py:78-79, 135-139; edsr_arch.py:44-48; rcan_arch.py:40-42;
