@@ -127,6 +127,13 @@ SIGNATURES = {
     'sr_l1_loss_workspace': (_sz, [_i64]),
     'sr_pixel_loss': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     'sr_pixel_loss_workspace': (_sz, [_i64]),
+    'sr_maxpool2_fwd': (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'sr_maxpool2_bwd': (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'sr_gram_kblock': (_i, []),
+    'sr_gram_splits': (_i, [_i]),
+    'sr_gram_workspace': (_sz, [_i, _i, _i]),
+    'sr_gram_fwd': (_i, [_i, _vp, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
+    'sr_gram_bwd': (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp]),
     'sr_act_backward': (_i, [_i, _vp, _vp, _i64, _i, _f, _f, _vp, _vp]),
     'sr_row_scale': (_i, [_i, _vp, _i64, _i, _i, _vp, _vp, _vp]),
     'sr_adam_ema': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _vp]),

@@ -2,9 +2,9 @@
 from copy import deepcopy
 
 from ..utils.registry import LOSS_REGISTRY
-from .basic_loss import CharbonnierLoss, L1Loss, MSELoss, WeightedTVLoss
+from .basic_loss import CharbonnierLoss, L1Loss, MSELoss, PerceptualLoss, WeightedTVLoss
 
-__all__ = ['build_loss', 'L1Loss', 'MSELoss', 'CharbonnierLoss', 'WeightedTVLoss']
+__all__ = ['build_loss', 'L1Loss', 'MSELoss', 'CharbonnierLoss', 'WeightedTVLoss', 'PerceptualLoss']
 
 
 def build_loss(opt):

@@ -8,11 +8,16 @@ reduction='none', bf16 predictions, WeightedTVLoss — runs on the streaming ker
 csrc/loss.hip (sr_pixel_loss): one pass over pred / target that writes the gradient, plus a
 weight-sum pass for the weighted mean.  Only a weight map that itself requires grad, or one of
 another shape, goes through plain torch ops with the reference's formula.
+
+PerceptualLoss (basic_loss.py:147-253): VGG features of both images (archs/vgg_arch.py), the criterion on
+the NHWC feature arrays through sr_pixel_loss, the style term on the Gram matrices of ops/perceptual.py.
 """
 import torch
 from torch import nn as nn
 
 from .. import _lib
+from ..archs.vgg_arch import VGGFeatureExtractor
+from ..ops import perceptual as P
 from ..utils.registry import LOSS_REGISTRY
 
 _reduction_modes = ['none', 'mean', 'sum']
@@ -202,3 +207,106 @@ class WeightedTVLoss(L1Loss):
         y_diff = super().forward(pred[:, :, :-1, :], pred[:, :, 1:, :], weight=y_weight)
         x_diff = super().forward(pred[:, :, :, :-1], pred[:, :, :, 1:], weight=x_weight)
         return x_diff + y_diff
+
+
+class _FeatureTerms(torch.autograd.Function):
+    """Both terms of one tapped layer from the prediction's feature map xf: the criterion against the
+    target's map gf (sr_pixel_loss, which leaves d/dxf) and the Gram matrix of xf.  The backward is the
+    Gram GEMM with the criterion's gradient, times its upstream scalar, added in the GEMM's store
+    (sr_gram_bwd's beta * res) instead of a separate accumulation pass over the feature map."""
+
+    @staticmethod
+    def forward(ctx, xf, gf, kind, reduction):
+        ctx.set_materialize_grads(False)
+        xf, gf = xf.contiguous(), gf.contiguous()
+        lib = _lib.load()
+        ws_bytes = lib.sr_pixel_loss_workspace(xf.numel())
+        ws = torch.empty(ws_bytes // 8 + 1, device=xf.device, dtype=torch.float64)
+        loss = torch.empty((), device=xf.device, dtype=torch.float32)
+        grad = torch.empty_like(xf)
+        _lib.check(
+            lib.sr_pixel_loss(kind, _REDUCE[reduction], _lib.dtype_code(xf.dtype), _lib.dtype_code(gf.dtype),
+                              _lib.ptr(xf), _lib.ptr(gf), None, 0, 1, 1, 1, xf.numel(), 1.0, 0.0, _lib.ptr(loss), None,
+                              _lib.ptr(grad), _lib.ptr(ws), ws_bytes, _lib.stream()))
+        ctx.scale = P.gram_scale(xf)
+        ctx.save_for_backward(xf, grad)
+        return loss, P.gram_fwd_raw(xf, ctx.scale)
+
+    @staticmethod
+    def backward(ctx, g_loss, dG):
+        xf, grad = ctx.saved_tensors
+        res = None if g_loss is None else (grad * g_loss).to(grad.dtype)
+        if dG is None:
+            return res, None, None, None
+        return P.gram_bwd_raw(xf, dG.float().contiguous(), ctx.scale, res=res, beta=1.0), None, None, None
+
+
+@LOSS_REGISTRY.register()
+class PerceptualLoss(nn.Module):
+    """Perceptual loss with the style loss (basic_loss.py:147-253).
+
+    ``layer_weights``: {VGG layer name: weight}; ``criterion``: 'l1' | 'l2' | 'fro'.  ``forward(x, gt)``
+    returns ``(percep_loss, style_loss)``, each None when its weight is 0.  ``pretrain_path`` / ``pretrained``
+    go to the VGGFeatureExtractor: the weights come from a file, nothing is downloaded."""
+
+    def __init__(self,
+                 layer_weights,
+                 vgg_type='vgg19',
+                 use_input_norm=True,
+                 range_norm=False,
+                 perceptual_weight=1.0,
+                 style_weight=0.,
+                 criterion='l1',
+                 pretrain_path=None,
+                 pretrained=True):
+        super().__init__()
+        self.perceptual_weight = perceptual_weight
+        self.style_weight = style_weight
+        self.layer_weights = layer_weights
+        self.criterion_type = criterion
+        if criterion == 'l1':
+            self._kind, self._reduction = _lib.LOSS_L1, 'mean'
+        elif criterion == 'l2':
+            self._kind, self._reduction = _lib.LOSS_MSE, 'mean'
+        elif criterion == 'fro':
+            self._kind, self._reduction = _lib.LOSS_MSE, 'sum'  # the square root follows
+        else:
+            raise NotImplementedError(f'{criterion} criterion has not been supported.')
+        self.vgg = VGGFeatureExtractor(layer_name_list=list(layer_weights.keys()), vgg_type=vgg_type,
+                                       use_input_norm=use_input_norm, range_norm=range_norm,
+                                       pretrain_path=pretrain_path, pretrained=pretrained)
+
+    def _finish(self, v):
+        return v.sqrt() if self.criterion_type == 'fro' else v
+
+    def _criterion(self, a, b):
+        # without a weight map the layout does not matter: NHWC features and Gram matrices are flat arrays
+        return self._finish(_PixelLossFused.apply(a, b, None, self._kind, self._reduction, 1.0, 0.0))
+
+    def forward(self, x, gt):
+        if not x.is_cuda or not gt.is_cuda:
+            raise NotImplementedError(_CPU_MESSAGE)
+        x_features = self.vgg(x)
+        with torch.no_grad():
+            gt_features = self.vgg(gt.detach())
+        want_p, want_s = self.perceptual_weight > 0, self.style_weight > 0
+        percep_loss, style_loss = (0 if want_p else None), (0 if want_s else None)
+        for k in x_features.keys():
+            xf, gf, w = x_features[k], gt_features[k], self.layer_weights[k]
+            if want_p and want_s and xf.requires_grad:
+                lp, gram_x = _FeatureTerms.apply(xf, gf, self._kind, self._reduction)
+                lp = self._finish(lp)
+            else:
+                lp = self._criterion(xf, gf) if want_p else None
+                gram_x = P.gram(xf) if want_s else None
+            if want_p:
+                percep_loss = percep_loss + lp * w
+            if want_s:
+                with torch.no_grad():
+                    gram_gt = P.gram(gf)
+                style_loss = style_loss + self._criterion(gram_x, gram_gt) * w
+        if want_p:
+            percep_loss = percep_loss * self.perceptual_weight
+        if want_s:
+            style_loss = style_loss * self.style_weight
+        return percep_loss, style_loss

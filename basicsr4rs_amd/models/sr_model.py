@@ -2,7 +2,8 @@
 basicsr/models/srrs_model.py:33-88).
 
 The train step ``optimize_parameters`` is the north-star hot path: zero_grad -> net_g
-forward on the HIP engine -> L1 (fused HIP reduction + gradient) -> backward (HIP conv
+forward on the HIP engine -> L1 (fused HIP reduction + gradient), optionally the perceptual / style
+terms (losses/basic_loss.py:PerceptualLoss) -> backward (HIP conv
 dgrad/wgrad; bucketed RCCL all-reduce launched from backward hooks when distributed) ->
 one fused Adam + EMA kernel over the flat parameter vector.  No host synchronisation
 inside the step (the loss log is reduced when read).
@@ -35,8 +36,6 @@ class SRModel(BaseModel):
     def build_optional_loss(self, opt_dict, key):
         if key not in opt_dict or opt_dict[key] is None:
             return None
-        if key == 'perceptual_opt':
-            raise NotImplementedError('PerceptualLoss needs pretrained VGG weights; out of scope (SURVEY.md §2a)')
         return build_loss(opt_dict[key]).to(self.device)
 
     def __init__(self, opt):
@@ -117,6 +116,21 @@ class SRModel(BaseModel):
     def _fused_step(self):
         return hasattr(self.optimizer_g, 'device_step')
 
+    def _perceptual_terms(self, l_total, loss_dict):
+        """l_percep / l_style of ``train.perceptual_opt`` (basicsr/models/sr_model.py:102-110) added to the
+        total and the log; the VGG features are computed in the net's autocast mode (bf16 with use_amp)."""
+        if not self.cri_perceptual:
+            return l_total
+        with torch.autocast('cuda', dtype=torch.bfloat16, enabled=self.use_amp):
+            l_percep, l_style = self.cri_perceptual(self.output, self.gt)
+        if l_percep is not None:
+            l_total = l_total + l_percep
+            loss_dict['l_percep'] = l_percep
+        if l_style is not None:
+            l_total = l_total + l_style
+            loss_dict['l_style'] = l_style
+        return l_total
+
     def _step_body(self, before_backward=None):
         """Device work of one train step (everything a captured replay re-executes).
         ``before_backward(loss) -> loss`` runs between the loss and backward (the segmented
@@ -130,6 +144,7 @@ class SRModel(BaseModel):
             l_pix = self.cri_pix(self.output, self.gt)
             l_total += l_pix
             loss_dict['l_pix'] = l_pix
+        l_total = self._perceptual_terms(l_total, loss_dict)
         if before_backward is not None:
             l_total = before_backward(l_total)
         # weight gradients on a side stream, joined here

@@ -51,6 +51,7 @@ class SRRSModel(SRModel):
             l_pix = self.cri_pix(self.output, self.gt)
             l_total += l_pix
             loss_dict['l_pix'] = l_pix
+        l_total = self._perceptual_terms(l_total, loss_dict)
         self.log_dict = self.reduce_loss_dict(loss_dict)
         if not torch.isfinite(l_total).item():
             print('Loss is NaN or Inf. Skipping optimizer step.')

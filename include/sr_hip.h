@@ -365,6 +365,41 @@ int sr_pixel_loss(int kind, int reduction, int pred_dtype, int target_dtype, con
                   const float* weight, int weight_channels, int N, int C, int H, int W, float loss_weight, float eps,
                   float* loss, void* out, void* grad, void* workspace, size_t ws_bytes, void* stream);
 size_t sr_pixel_loss_workspace(int64_t n);
+/* ---------------------------------------------------------------------------------
+ * Perceptual / style loss kernels (csrc/perceptual.hip; PerceptualLoss of basicsr/losses/basic_loss.py:147-253
+ * over the VGGFeatureExtractor of basicsr/archs/vgg_arch.py).  Feature maps are dense NHWC of dtype
+ * (SR_F32 / SR_BF16), 16-byte aligned, C a multiple of 8.  Fixed summation orders, no atomics: two calls
+ * give identical bits; nothing allocates or synchronises.  SR_EINVAL for null pointers, non-positive sizes,
+ * an unsupported dtype / stride / channel count or a misaligned pointer, SR_ETOOBIG when a tensor reaches
+ * 2^31 bytes; nothing is launched then.
+ *
+ * sr_maxpool2_fwd: nn.MaxPool2d(kernel_size=2, stride) with stride 1 or 2, no padding, floor mode:
+ *   y [N, Ho, Wo, C], Ho = (H - 2) / stride + 1.  The first maximum in row-major window order wins and a
+ *   NaN propagates, as torch.
+ * sr_maxpool2_bwd: dx [N, H, W, C] of the same, all of it written: dy goes to the element the forward chose
+ *   (recomputed from x with the forward's rule), overlapping stride-1 windows sum (fp32, fixed order), a
+ *   row / column the floor drops is zero.
+ * ------------------------------------------------------------------------------- */
+int sr_maxpool2_fwd(int dtype, const void* x, int N, int H, int W, int C, int stride, void* y, void* stream);
+int sr_maxpool2_bwd(int dtype, const void* x, const void* dy, int N, int H, int W, int C, int stride, void* dx,
+                    void* stream);
+/* Gram matrix per image: G[n] = F[n]^T F[n] * scale, F [N, HW, C] of dtype (C <= 512), G fp32 [N, C, C]
+ * (basic_loss.py:240-253 with scale = 1 / (C * H * W)); MFMA bf16 16x16x32 / f32 16x16x4 as the convs.
+ * K = HW is split over sr_gram_splits(HW) blocks per image of sr_gram_kblock() * m rows each (m the smallest
+ * integer that keeps the splits at 64 or fewer; the last block takes the rest); with more than one split
+ * the fp32 partials go to ws (sr_gram_workspace bytes, 4-byte aligned; 0 and ws may be NULL with one
+ * split) and are summed in a fixed order. */
+int sr_gram_kblock(void);
+int sr_gram_splits(int HW);
+size_t sr_gram_workspace(int N, int HW, int C);
+int sr_gram_fwd(int dtype, const void* F, int N, int HW, int C, float scale, float* G, void* ws, size_t ws_bytes,
+                void* stream);
+/* dF[n] = alpha * F[n] (dG[n] + dG[n]^T) + beta * res[n] in F's dtype: the gradient of sr_gram_fwd (alpha
+ * carries its scale) plus, optionally, another gradient of the same feature map in the same store (res:
+ * F's shape and dtype, may be NULL).  dG fp32 [N, C, C], symmetrised while it is staged; products and sums
+ * in fp32 (f32 MFMA for both dtypes). */
+int sr_gram_bwd(int dtype, const void* F, const float* dG, const void* res, int N, int HW, int C, float alpha,
+                float beta, void* dF, void* stream);
 /* Activation backward: out = alpha * dy * (y > 0 ? 1 : neg), neg = 0 for SR_ACT_RELU, slope for
  * SR_ACT_LRELU, 1 for SR_ACT_NONE; y is the activation OUTPUT (same sign as its input). */
 int sr_act_backward(int dtype, const void* dy, const void* y, int64_t n, int act, float slope, float alpha,
