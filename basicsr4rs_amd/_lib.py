@@ -71,6 +71,10 @@ class WgradDesc(ctypes.Structure):
                 ('scale', _f), ('in_up', _i), ('ksize', _i), ('accumulate', _i)]
 
 
+class WgradItem(ctypes.Structure):
+    _fields_ = [('dy', _vp), ('x', _vp), ('dw', _vp), ('db', _vp), ('scale', _f)]
+
+
 class PrepItem(ctypes.Structure):
     _fields_ = [('w', _vp), ('bias', _vp), ('Cout_real', _i), ('Cin_real', _i), ('Cout', _i), ('Cin', _i),
                 ('out_ps', _i), ('ksize', _i), ('row_map', _vp), ('col_map', _vp), ('wf', _vp), ('wd', _vp),
@@ -107,6 +111,11 @@ SIGNATURES = {
     'sr_conv3x3_wgrad_workspace': (_sz, [ctypes.POINTER(WgradDesc)]),
     'sr_conv3x3_wgrad': (_i, [ctypes.POINTER(WgradDesc), _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     'sr_conv3x3_wgrad_reduce': (_i, [ctypes.POINTER(WgradDesc), _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    'sr_conv3x3_wgrad_pair_ok': (_i, [ctypes.POINTER(WgradDesc)]),
+    'sr_conv3x3_wgrad_pair_workspace': (_sz, [ctypes.POINTER(WgradDesc)]),
+    'sr_conv3x3_wgrad_pair_plan': (_i, [ctypes.POINTER(WgradDesc), ctypes.POINTER(_i), ctypes.POINTER(_i),
+                                        ctypes.POINTER(_i)]),
+    'sr_conv3x3_wgrad_pair': (_i, [ctypes.POINTER(WgradDesc), ctypes.POINTER(WgradItem), _vp, _sz, _vp]),
     'sr_conv_prep_blocks': (_i, [ctypes.POINTER(PrepItem)]),
     'sr_conv_prep_batch': (_i, [_i, _vp, _vp, _i, _i, _vp]),
     'sr_conv3x3_prep': (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -18,6 +18,9 @@ SR_CA_DOT             1: channel-attention dots from the next block's dgrad epil
 SR_DCN_BWD_FUSED      0: the DCN backward through the dcols matrix
 SR_CONV_KPAD          0: no K-padded weight images for the 184-channel 3x3 convs (the 64-channel halo kernel)
 SR_STEP_TRACE         host time stamps of the segmented DDP graph step (a file path)
+SR_WG_PAIR            0: a residual block's two weight gradients as two launches instead of the paired one
+                      (k > 0: bias-role blocks of k splits); read by the library's knob table, listed here
+                      because it changes what ops.conv._ResBlock launches
 """
 import os
 

@@ -2633,7 +2633,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad_ring_kernel(WgArgs a) {
 // rows arrive as three 32-row pieces, the third (rows 34..65) rewriting 30 rows of the second with the
 // same bytes.  Image edges and rows outside the image read zeros (out-of-range buffer offsets).  Bias:
 // bias-role blocks after the tile blocks, each summing dy over bias_group splits.  Output: the pp
-// kernel's [S][9][Cout][Cin] slab (same reduce), staged through LDS for 16-B row stores.
+// kernel's [S][9][Cout][Cin] slab (same reduce), staged through LDS for 16-B row stores.  One grid can
+// hold two problems of one geometry (WgArgs.pair_nt, sr_conv3x3_wgrad_pair: both convs of a residual block
+// at half the splits each; DESIGN note 40).
 // ------------------------------------------------------------------------------------
 // Compile-time loop: f(std::integral_constant<int, I>) for I = 0 .. N - 1 (fully unrolled by construction;
 // a #pragma unroll loop this large exceeds the unroller's threshold and its arrays go to scratch).
@@ -2658,7 +2660,25 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wgrad_row3_kernel(WgArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = w >> 1, wc = w & 1;
-  const uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
+  uint32_t b = xcd_remap(blockIdx.x, gridDim.x);
+  if (a.pair_nt > 0) {
+    // two problems of one geometry in one grid, [tiles 0][tiles 1][bias 0][bias 1]: pick this block's
+    // problem (block-uniform) and rebase b to its index in that problem's own single-launch grid
+    const uint32_t nt = (uint32_t)a.pair_nt, nbias = (gridDim.x - 2 * nt) >> 1;
+    bool second;
+    if (b < 2 * nt) {
+      second = b >= nt;
+      b -= second ? nt : 0;
+    } else {
+      const uint32_t bb = b - 2 * nt;
+      second = bb >= nbias;
+      b = nt + bb - (second ? nbias : 0);
+    }
+    if (second) {
+      a.dy = a.dy1; a.x = a.x1; a.ws = a.ws1; a.wsb = a.wsb1;
+      a.dy_bytes = a.dy1_bytes; a.x_bytes = a.x1_bytes;
+    }
+  }
   const int ntile = 3 * a.tiles_co * a.tiles_ci;
   const __amdgpu_buffer_rsrc_t dyr = make_rsrc(a.dy, a.dy_bytes);
   const __amdgpu_buffer_rsrc_t xr = make_rsrc(a.x, a.x_bytes);
@@ -3007,9 +3027,12 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_g_kernel(const float* ws, c
                                                               int S, int Cout, int Cin, int Cout_real, int Cin_real,
                                                               int out_ps, int taps, const int* co_map,
                                                               const int* ci_map, float scale, int wblocks,
-                                                              int accumulate) {
+                                                              int accumulate, WgReduce2 p2) {
   extern __shared__ f32x4 red[];  // nw * 64 entries (dynamic: a 4-wave block needs 4 KB, so it can
                                   // share a CU with the 158 KB pph kernel when it runs on a side stream)
+  if (blockIdx.y) {  // grid row 1: the second item of a paired reduce (same shape, S and order of the sums)
+    ws = p2.ws; wsb = p2.wsb; dw = p2.dw; db = p2.db; scale = p2.scale;
+  }
   const int nw = (int)(blockDim.x >> 6);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int r2 = out_ps > 0 ? out_ps * out_ps : 1;
@@ -3842,6 +3865,19 @@ hipError_t launch_wg_row3(WgArgs a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// Two problems of one geometry (a: problem 0 and the dy1 / x1 / ws1 / wsb1 set, both wsb or neither) in one grid:
+// each problem's tile blocks contiguous and split-major as in its own launch, then the bias-role blocks of both.
+hipError_t launch_wg_row3_pair(WgArgs a, int bias_group, hipStream_t s) {
+  const int S = a.splits;
+  a.tiles_co = a.Cout / 256;
+  a.tiles_ci = a.Cin / 128;
+  a.bias_group = bias_group;
+  a.pair_nt = S * 3 * a.tiles_co * a.tiles_ci;
+  const int nb = 2 * a.pair_nt + (a.wsb ? 2 * ((S + bias_group - 1) / bias_group) * a.tiles_co : 0);
+  hipLaunchKernelGGL(conv3x3_wgrad_row3_kernel, dim3(nb), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 // Weight gradients with >= 128 channels each side that are not multiples of 128 (SwinIR linears
 // 184 / 368 / 576, its 184-channel 3x3 convs): the 256x256 phase-interleaved kernel with partial
 // tiles (columns past Cout / Cin read neighbouring data that only feeds the discarded rows /
@@ -4015,6 +4051,35 @@ void wgrad_plan(const sr_conv3x3_wgrad_desc* d, int* splits, int* kper) {
     S = (1024 + tiles / 2) / tiles;
   }
   plan_splits(M, S, (M + 255) / 256, splits, kper);  // at least 256 pixels per split
+}
+
+// Paired kernel-row wgrad (sr_conv3x3_wgrad_pair): the two convs of a residual block, one geometry, in one
+// launch.  One 256-block wave then holds both problems' tiles, so each gets half the splits of its own launch
+// (EDSR-L body: 20 instead of 39): the DMA prologue and the slab store are paid once per ~103 K-steps instead
+// of ~52, the slab and its reduce traffic halve, and one reduce launch serves both.  Knob SR_WG_PAIR=0: off
+// (sr_conv3x3_wgrad_pair_ok answers 0; A/B and tests); k > 0: bias-role blocks of k splits (default 3: S 20
+// in 254 blocks; 2 gives S 19 in 248 and measured 0.24 ms slower per EDSR step, DESIGN note 40).  The plan is a
+// function of the descriptor and the knobs alone.
+int wg_pair_bg() {
+  const int k = sr_knob(K_WG_PAIR);
+  return k > 0 && k <= 64 ? k : 3;
+}
+bool wg_pair_ok(const sr_conv3x3_wgrad_desc* d) {
+  if (!d || d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Cin <= 0 || d->Cout <= 0) return false;
+  if (sr_knob(K_WG_PAIR) == 0 || !wg_use_row3(d) || d->out_ps != 0) return false;
+  if (d->ldx % 8 || d->ldy % 8 || d->xcoff % 8 || d->ycoff % 8) return false;
+  const int cin_real = d->Cin_real > 0 ? d->Cin_real : d->Cin;
+  if (cin_real % 4) return false;  // the grouped slab reduce
+  const int tco = d->Cout / 256;
+  return 3 * tco * (d->Cin / 128) + tco <= 128;  // one split of both problems within one 256-block wave
+}
+// Largest S with 2 S ntile + 2 ceil(S / bg) tco <= 256, then whole 64-pixel steps per split as plan_splits
+void wgrad_pair_plan(const sr_conv3x3_wgrad_desc* d, int* splits, int* kper, int* blocks) {
+  const int M = d->N * d->H * d->W, tco = d->Cout / 256, ntile = 3 * tco * (d->Cin / 128), bg = wg_pair_bg();
+  int S = 128 / ntile;
+  while (S > 1 && S * ntile + (S + bg - 1) / bg * tco > 128) --S;
+  plan_splits(M, S, M / 64, splits, kper);
+  *blocks = 2 * (*splits * ntile + (*splits + bg - 1) / bg * tco);
 }
 
 // Shape / flag fields of FwdArgs from a descriptor (no pointers; validated by the caller).
@@ -4240,8 +4305,9 @@ size_t sr_conv3x3_wgrad_workspace(const sr_conv3x3_wgrad_desc* d) {
 namespace sr_conv __attribute__((visibility("hidden"))) {
 // The slab reduce of a sr_conv3x3_wgrad call (S splits of its plan, slab ws, bias slab wsb)
 int wgrad_reduce_launch(const sr_conv3x3_wgrad_desc* d, int S, int taps, const float* ws, const float* wsb, float* dw,
-                        float* db, const int* co_map, const int* ci_map, hipStream_t s) {
+                        float* db, const int* co_map, const int* ci_map, hipStream_t s, const WgReduce2* second) {
   const int acc1 = d->accumulate & 1;
+  const WgReduce2 p2 = second ? *second : WgReduce2{};
   const int Cout_real = d->Cout_real > 0 ? d->Cout_real : d->Cout;
   const int Cin_real = d->Cin_real > 0 ? d->Cin_real : d->Cin;
   const int64_t total = (int64_t)Cout_real * Cin_real;
@@ -4261,17 +4327,19 @@ int wgrad_reduce_launch(const sr_conv3x3_wgrad_desc* d, int S, int taps, const f
     const int nw = P * gpw / 64 > 0 ? P * gpw / 64 : 1;
     const int wblocks = (int)((groups + gpw - 1) / gpw);
     const int bblocks = db ? (Cout_real + 63) / 64 : 0;
-    const dim3 grid((unsigned)(wblocks + bblocks)), blk((unsigned)(nw * 64));
+    const dim3 grid((unsigned)(wblocks + bblocks), second ? 2u : 1u), blk((unsigned)(nw * 64));
 #define SR_RG(G, T, ...)                                                                                        \
   hipLaunchKernelGGL((wgrad_reduce_g_kernel<G, T, ##__VA_ARGS__>), grid, blk, (size_t)nw * 64 * 16, s, (const float*)ws, (const float*)wsb, dw, db, \
                      S, d->Cout, d->Cin, Cout_real, Cin_real, d->out_ps, taps, co_map, ci_map, d->scale, wblocks,  \
-                     acc1)
+                     acc1, p2)
     // (the tr arm is never taken under the !tr guard above: the row-streaming slab keeps wgrad_reduce_tr_kernel; its
     // three instantiations stay so that the set of kernels in the library is the parent's)
     if (tr) { if (gpw == 64) SR_RG(64, true); else if (gpw == 32) SR_RG(32, true); else SR_RG(16, true); }
     else if (cig) { if (gpw == 64) SR_RG(64, false, true); else if (gpw == 32) SR_RG(32, false, true); else SR_RG(16, false, true); }
     else { if (gpw == 64) SR_RG(64, false); else if (gpw == 32) SR_RG(32, false); else SR_RG(16, false); }
 #undef SR_RG
+  } else if (second) {
+    return sr_fail(SR_EINVAL, "conv3x3_wgrad reduce: a paired reduce needs the grouped slab reduce (Cin_real % 4 == 0, no maps)");
   } else if (tr) {
     const int64_t work4 = (int64_t)taps * Cin_real * ((Cout_real + 3) / 4);
     const int wblocks = (int)((work4 + 63) / 64);
@@ -4360,6 +4428,64 @@ int sr_conv3x3_wgrad_reduce(const sr_conv3x3_wgrad_desc* d, void* workspace, siz
   float* ws = (float*)workspace;
   float* wsb = db ? ws + (size_t)S * taps * d->Cout * d->Cin : nullptr;
   return wgrad_reduce_launch(d, S, taps, ws, wsb, dw, db, co_map, ci_map, (hipStream_t)stream);
+}
+
+int sr_conv3x3_wgrad_pair_ok(const sr_conv3x3_wgrad_desc* d) { return wg_pair_ok(d) ? 1 : 0; }
+
+int sr_conv3x3_wgrad_pair_plan(const sr_conv3x3_wgrad_desc* d, int* splits, int* kper, int* blocks) {
+  if (!d || !splits || !kper || !blocks) return sr_fail(SR_EINVAL, "conv3x3_wgrad_pair_plan: null pointer");
+  if (!wg_pair_ok(d)) return sr_fail(SR_EINVAL, "conv3x3_wgrad_pair_plan: descriptor not on the paired kernel-row wgrad");
+  wgrad_pair_plan(d, splits, kper, blocks);
+  return SR_OK;
+}
+
+// two slabs [S][9][Cout][Cin] + [S][Cout], item 1's after item 0's
+size_t sr_conv3x3_wgrad_pair_workspace(const sr_conv3x3_wgrad_desc* d) {
+  if (!wg_pair_ok(d)) return 0;
+  int S, kp, nb;
+  wgrad_pair_plan(d, &S, &kp, &nb);
+  return 2 * ((size_t)S * 9 * d->Cout * d->Cin + (size_t)S * d->Cout) * sizeof(float) + 256;
+}
+
+int sr_conv3x3_wgrad_pair(const sr_conv3x3_wgrad_desc* d, const sr_conv3x3_wgrad_item* items, void* workspace,
+                          size_t ws_bytes, void* stream) {
+  if (!d || !items || !workspace) return sr_fail(SR_EINVAL, "conv3x3_wgrad_pair: null pointer");
+  if (!wg_pair_ok(d)) return sr_fail(SR_EINVAL, "conv3x3_wgrad_pair: descriptor not on the paired kernel-row wgrad");
+  if (d->accumulate & 2) return sr_fail(SR_EINVAL, "conv3x3_wgrad_pair: no slab-only form (accumulate bit 1)");
+  for (int i = 0; i < 2; ++i)
+    if (!items[i].dy || !items[i].x || !items[i].dw) return sr_fail(SR_EINVAL, "conv3x3_wgrad_pair: null item pointer");
+  if (!items[0].db != !items[1].db) return sr_fail(SR_EINVAL, "conv3x3_wgrad_pair: both db or neither");
+  if (ws_bytes < sr_conv3x3_wgrad_pair_workspace(d)) return sr_fail(SR_EINVAL, "conv3x3_wgrad_pair: workspace too small");
+  const int M = d->N * d->H * d->W;
+  const size_t xb = (size_t)M * d->ldx * 2, dyb = (size_t)M * d->ldy * 2;
+  if (xb >= 0x80000000ull || dyb >= 0x80000000ull)
+    return sr_fail(SR_ETOOBIG, "conv3x3_wgrad_pair: tensor >= 2 GiB (split the batch)");
+  int S, kp, nb;
+  wgrad_pair_plan(d, &S, &kp, &nb);
+  const bool bias = items[0].db != nullptr;
+  const size_t slab = (size_t)S * 9 * d->Cout * d->Cin, per = slab + (size_t)S * d->Cout;
+  float* ws0 = (float*)workspace;
+  float* ws1 = ws0 + per;
+  WgArgs a{};
+  a.dy = items[0].dy; a.x = items[0].x; a.ws = ws0; a.wsb = bias ? ws0 + slab : nullptr;
+  a.dy1 = items[1].dy; a.x1 = items[1].x; a.ws1 = ws1; a.wsb1 = bias ? ws1 + slab : nullptr;
+  a.dy_bytes = a.dy1_bytes = (uint32_t)dyb; a.x_bytes = a.x1_bytes = (uint32_t)xb;
+  a.taps = 9; a.tap0 = 0;
+  a.N = d->N; a.H = d->H; a.W = d->W; a.M = M;
+  a.Cin = d->Cin; a.ldx = d->ldx; a.xcoff = d->xcoff;
+  a.Cout = d->Cout; a.ldy = d->ldy; a.ycoff = d->ycoff; a.out_ps = 0;
+  a.in_up = 1;
+  a.splits = S; a.kper = kp;
+  a.fd_W = make_fastdiv(d->W); a.fd_H = make_fastdiv(d->H);
+  a.fd_cps = make_fastdiv(1);
+  a.stamps = g_sr_stamps;
+  hipStream_t s = (hipStream_t)stream;
+  const hipError_t e = launch_wg_row3_pair(a, wg_pair_bg(), s);
+  if (e != hipSuccess) return sr_check(e, "conv3x3_wgrad_pair launch");
+  sr_conv3x3_wgrad_desc d0 = *d;
+  d0.scale = items[0].scale;
+  const WgReduce2 p2{a.ws1, a.wsb1, items[1].dw, items[1].db, items[1].scale};
+  return wgrad_reduce_launch(&d0, S, 9, a.ws, a.wsb, items[0].dw, items[0].db, nullptr, nullptr, s, &p2);
 }
 
 int sr_conv_prep_mapped(int dtype, int ksize, const float* w, const float* bias, int Cout_real, int Cin_real,

@@ -90,6 +90,24 @@ struct WgArgs {
   int bias_fused;  // pp kernel: no bias-role blocks; the centre-tap, first-ci-tile blocks sum dy as well
   FastDiv fd_W, fd_H, fd_cps;
   unsigned long long* stamps;  // diagnostics (SR_BAND_STAMPS builds): per-block phase cycles
+  // Kernel-row wgrad over TWO problems of one geometry in one grid (sr_conv3x3_wgrad_pair): pair_nt > 0 is
+  // the tile-block count of each problem (splits x tiles) and the grid is [tiles 0][tiles 1][bias 0][bias 1];
+  // the operands above are problem 0's, these problem 1's.  0: one problem, the fields are unused.
+  int pair_nt;
+  uint32_t dy1_bytes, x1_bytes;
+  const void* dy1;
+  const void* x1;
+  float* ws1;
+  float* wsb1;
+};
+
+// Second item of a paired slab reduce (wgrad_reduce_g_kernel, grid y = 1): its slab, outputs and scale.
+struct WgReduce2 {
+  const float* ws;
+  const float* wsb;
+  float* dw;
+  float* db;
+  float scale;
 };
 
 // Kernel family sr_conv3x3_fwd launches for a call (dispatch, kernel names and the
@@ -134,7 +152,10 @@ hipError_t launch_wg_tile(const WgArgs& a, bool bf16, hipStream_t s);           
 hipError_t launch_wg_big(WgArgs a, const sr_conv3x3_wgrad_desc* d, hipStream_t s);   // conv3x3_wgrad_tile.hip
 hipError_t launch_wg_ring(WgArgs a, const sr_conv3x3_wgrad_desc* d, hipStream_t s);  // conv3x3_wgrad_ring.hip
 hipError_t launch_wg_row3(WgArgs a, hipStream_t s);                                  // conv3x3_wgrad_ring.hip
+hipError_t launch_wg_row3_pair(WgArgs a, int bias_group, hipStream_t s);             // conv3x3_wgrad_ring.hip
+// (second: the other item of a pair, reduced by the same launch with d->scale for the first; no maps)
 int wgrad_reduce_launch(const sr_conv3x3_wgrad_desc* d, int S, int taps, const float* ws, const float* wsb, float* dw,
-                        float* db, const int* co_map, const int* ci_map, hipStream_t s);  // conv3x3_wgrad_reduce.hip
+                        float* db, const int* co_map, const int* ci_map, hipStream_t s,
+                        const WgReduce2* second = nullptr);  // conv3x3_wgrad_reduce.hip
 
 }  // namespace sr_conv

@@ -27,6 +27,7 @@ enum SrKnob {
   K_SWIN_ATTN_DBG,  // SR_SWIN_ATTN_DBG: fused attention timing ablations (wrong results)
   K_WG_ROW3,        // SR_WG_ROW3: 0 = the kernel-row wgrad off (pp kernel), > 0 = its bias-role group size
   K_PPH_GRID,       // SR_PPH_GRID: blocks of the persistent pph forward grid (default: the CU count)
+  K_WG_PAIR,        // SR_WG_PAIR: 0 = the paired kernel-row wgrad off (two single calls), > 0 = its bias-role group size
   K_COUNT
 };
 int sr_knob(SrKnob k);

@@ -567,6 +567,67 @@ def _wgrad_launch(lib, d, dy, x, ws_bytes, tw, tb, cin_real, cout_real, need_bia
     return dw, db
 
 
+def conv_wgrad_pair_raw(items, N, H, W, cin, cin_real, cout, cout_real):
+    """Both weight gradients of a residual block (one geometry) by one split-K launch and one reduce
+    launch (sr_conv3x3_wgrad_pair), accumulated straight into the FlatParams ``.grad`` views.
+
+    ``items``: two ``(dy, x, scale, (weight, bias))``.  Returns False, having launched nothing, where the
+    paired form does not run (sr_conv3x3_wgrad_pair_ok, or a parameter without a flat-gradient target):
+    the caller then makes its two conv_wgrad_raw calls.  Gradient-ready callbacks fire in item order."""
+    (dy0, x0, _, _), (dy1, x1, _, _) = items
+    if not (dy0.shape == dy1.shape and x0.shape == x1.shape and dy0.dtype == x0.dtype == dy1.dtype == x1.dtype):
+        return False
+    d = _lib.WgradDesc()
+    d.dtype = _lib.dtype_code(x0.dtype)
+    d.N, d.H, d.W = N, H, W
+    d.Cin, d.Cin_real, d.ldx, d.xcoff = cin, cin_real, x0.shape[-1], 0
+    d.Cout, d.Cout_real, d.ldy, d.ycoff, d.out_ps = cout, cout_real, dy0.shape[-1], 0, 0
+    d.scale, d.in_up, d.ksize, d.accumulate = 1.0, 0, 3, 1
+    lib = _lib.load()
+    if not lib.sr_conv3x3_wgrad_pair_ok(d):
+        return False
+    targets = [(grad_target(p[0]), grad_target(p[1])) for _, _, _, p in items]
+    if any(t is None for tt in targets for t in tt):
+        return False
+    ws_bytes = lib.sr_conv3x3_wgrad_pair_workspace(d)
+    ready = tuple((lambda p=p: grad_ready(p)) for _, _, _, pp in items for p in pp)
+    # (a traced step stays single-stream; in 'reduce' mode the pair runs whole on the current stream)
+    side = async_side_stream(x0.device) if not ktrace.active() and async_mode() != 'reduce' else None
+    if side is not None:  # one fork for the pair; both dy held until the join (see conv_wgrad_raw)
+        side_launch(side, lambda: _wgrad_pair_launch(lib, d, items, targets, ws_bytes, cin_real, cout_real),
+                    (dy0, x0, dy1, x1), hold=(dy0, dy1), after=ready)
+        return True
+    _wgrad_pair_launch(lib, d, items, targets, ws_bytes, cin_real, cout_real)
+    for cb in ready:
+        cb()
+    return True
+
+
+def _wgrad_pair_launch(lib, d, items, targets, ws_bytes, cin_real, cout_real):
+    dev = items[0][1].device
+    ws = torch.empty(ws_bytes // 4 + 1, device=dev, dtype=torch.float32)
+
+    def pack(outs):
+        arr = (_lib.WgradItem * 2)()
+        for it, (dy, x, scale, _), (dw, db) in zip(arr, items, outs):
+            it.dy, it.x, it.dw, it.db, it.scale = dy.data_ptr(), x.data_ptr(), dw.data_ptr(), db.data_ptr(), scale
+        return arr
+
+    arr = pack(targets)
+    if ktrace.active():  # the relaunch closure must not accumulate into the live gradients
+        scratch = [(torch.empty_like(dw), torch.empty_like(db)) for dw, db in targets]
+        keep = (items, ws, scratch, pack(scratch))
+        relaunch = lambda k=keep: lib.sr_conv3x3_wgrad_pair(d, k[3], _lib.ptr(ws), ws_bytes, _lib.stream())  # noqa: E731
+    else:
+        relaunch = None
+    M = d.N * d.H * d.W
+    # per conv as conv_wgrad_raw: dy and x once, dW / db read-modify-written as fp32
+    nbytes = 2 * (items[0][1].element_size() * M * (d.Cout + d.Cin) + 8 * (9 * cin_real * cout_real + cout_real))
+    with ktrace.span(lib.sr_conv3x3_wgrad_kernel_name(d).decode() + '+reduce', 2 * 2.0 * M * 9 * cin_real * cout_real,
+                     nbytes, relaunch=relaunch, launches=1):
+        _lib.check(lib.sr_conv3x3_wgrad_pair(d, arr, _lib.ptr(ws), ws_bytes, _lib.stream()))
+
+
 def nchw_to_nhwc(x, cp, dtype, shift=None, scale=None):
     N, C, H, W = x.shape
     y = torch.empty(N, H, W, cp, device=x.device, dtype=dtype)
@@ -822,6 +883,13 @@ class _ResBlock(torch.autograd.Function):
         dz1 = torch.empty_like(t)
         conv_fwd_raw(dy, wd2, None, dz1, N, H, W, spec2.cout_p, spec2.cin_p, spec2.cin_p, alpha=rs, gate=t,
                      gate_slope=0.0)
+        # both weight gradients have their operands now: (dy, t) and (dz1, x), one geometry -> one launch
+        if (spec1.cin_p, spec1.cin, spec1.cout_p, spec1.cout) == (spec2.cin_p, spec2.cin, spec2.cout_p, spec2.cout) and \
+                conv_wgrad_pair_raw(((dy, t, rs, (w2, b2)), (dz1, x, 1.0, (w1, b1))), N, H, W, spec2.cin_p, spec2.cin,
+                                    spec2.cout_p, spec2.cout):
+            dx = torch.empty_like(x)
+            conv_fwd_raw(dz1, wd1, None, dx, N, H, W, spec1.cout_p, spec1.cin_p, spec1.cin_p, res=dy, beta=1.0)
+            return dx, None, None, None, None, None, None, None
         dw2, db2 = conv_wgrad_raw(dy, t, N, H, W, spec2.cin_p, spec2.cin, spec2.cout_p, spec2.cout, scale=rs,
                                   params=(w2, b2))
         dx = torch.empty_like(x)

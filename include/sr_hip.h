@@ -202,6 +202,27 @@ int sr_conv3x3_wgrad(const sr_conv3x3_wgrad_desc* d, const void* dy, const void*
 int sr_conv3x3_wgrad_reduce(const sr_conv3x3_wgrad_desc* d, void* workspace, size_t ws_bytes, float* dw, float* db,
                             const int* co_map, const int* ci_map, void* stream);
 
+/* Two weight gradients of ONE geometry in one split-K launch and one reduce launch (the two convs of a
+ * residual block): the descriptor gives the shared geometry, dtype and accumulate bit 0 (its scale is
+ * unused), each item its operands, outputs and scale; both db are non-NULL or both NULL.  Each result is
+ * deterministic and independent of the other item.
+ * sr_conv3x3_wgrad_pair_ok: 1 exactly where the paired form runs (bf16 3x3 on the kernel-row wgrad, no
+ * pixel shuffle, no maps; knob SR_WG_PAIR=0: never), else the caller makes two sr_conv3x3_wgrad calls.
+ * sr_conv3x3_wgrad_pair_plan: the split plan (host-only query): splits per item, pixels per split and the
+ * blocks of the launch with bias gradients. */
+typedef struct sr_conv3x3_wgrad_item {
+  const void* dy;
+  const void* x;
+  float* dw;
+  float* db;
+  float scale;
+} sr_conv3x3_wgrad_item;
+int sr_conv3x3_wgrad_pair_ok(const sr_conv3x3_wgrad_desc* d);
+size_t sr_conv3x3_wgrad_pair_workspace(const sr_conv3x3_wgrad_desc* d);
+int sr_conv3x3_wgrad_pair_plan(const sr_conv3x3_wgrad_desc* d, int* splits, int* kper, int* blocks);
+int sr_conv3x3_wgrad_pair(const sr_conv3x3_wgrad_desc* d, const sr_conv3x3_wgrad_item* items, void* workspace,
+                          size_t ws_bytes, void* stream);
+
 /* Weight preparation from the nn.Conv2d parameter w[Cout_real][Cin_real][3][3] (fp32):
  *   wf[n][tap*Cin + ci]       forward GEMM rows (n = GEMM column, permuted by out_ps)
  *   wd[ci][tap'*Cout + n]     dgrad GEMM rows (spatially flipped, transposed)
