@@ -143,6 +143,24 @@ SIGNATURES = {
     'sr_gram_workspace': (_sz, [_i, _i, _i]),
     'sr_gram_fwd': (_i, [_i, _vp, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
     'sr_gram_bwd': (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp]),
+    'sr_gan_loss_workspace': (_sz, [_i64]),
+    'sr_gan_loss_block': (_i, [_i]),
+    'sr_gan_loss': (_i, [_i, _i, _vp, _i64, _f, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    'sr_conv4s2_prep': (_i, [_i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'sr_conv4s2_fwd': (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'sr_conv4s2_dgrad': (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'sr_conv4s2_wgrad_workspace': (_sz, [_i, _i, _i, _i, _i]),
+    'sr_conv4s2_wgrad_splits': (_i, [_i, _i, _i, _i, _i]),
+    'sr_conv4s2_wgrad': (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _sz, _vp]),
+    'sr_bn_workspace': (_sz, [_i64, _i]),
+    'sr_bn_blocks': (_i, [_i64]),
+    'sr_bn_stats': (_i, [_i, _vp, _i64, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'sr_bn_apply': (_i, [_i, _vp, _i64, _i, _vp, _vp, _i, _f, _vp, _vp, _i, _f, _vp, _vp]),
+    'sr_bn_bwd_reduce': (_i, [_i, _vp, _vp, _i64, _i, _vp, _vp, _i, _f, _vp, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    'sr_bn_bwd_dx': (_i, [_i, _vp, _vp, _i64, _i, _vp, _vp, _i, _f, _vp, _vp, _i, _f, _vp, _vp, _i, _vp, _vp]),
+    'sr_fc_fwd': (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    'sr_fc_dgrad': (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    'sr_fc_wgrad': (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     'sr_act_backward': (_i, [_i, _vp, _vp, _i64, _i, _f, _f, _vp, _vp]),
     'sr_row_scale': (_i, [_i, _vp, _i64, _i, _i, _vp, _vp, _vp]),
     'sr_adam_ema': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _vp]),

@@ -10,6 +10,8 @@
 //       one-channel map), folded in double and left in the workspace with the gradient scale
 //       loss_weight / denom -- the main pass reads it from there, so it never visits the host.
 //   loss_final_kernel : fold of the block partials in double (as l1_final_kernel of eltwise.hip).
+//   gan_loss_kernel : the GANLoss family (basicsr/losses/gan_loss.py:89-112: vanilla, lsgan, wgan, wgan_softplus,
+//       hinge) over a prediction of any shape, the same streaming pass and fold: the mean loss and its gradient.
 //
 // Every sum has a fixed order (per thread in element order, LDS tree per block, strided fold over the
 // blocks): no atomics, two runs are bit-identical, and the launches can be captured in a HIP graph.
@@ -209,6 +211,72 @@ __global__ void __launch_bounds__(PL_THREADS)
   if (threadIdx.x == 0) *loss = (float)(sum * lw / (denom_dev ? *denom_dev : denom_arg));
 }
 
+// GAN loss terms (basicsr/losses/gan_loss.py:89-112), one element x of the prediction -> (l, dl/dx).
+// FORM 0: BCE with logits against the label t, max(x, 0) - x t + log1p(exp(-|x|)), gradient sigmoid(x) - t;
+// FORM 1: (x - t)^2; FORM 2: sg * x; FORM 3: softplus(sg * x); FORM 4: relu(1 + sg * x).
+SR_DEV float gl_sigmoid(float z) {
+  const float e = expf(-fabsf(z));
+  return z >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+}
+template <int FORM>
+SR_DEV void gan_term(float x, float t, float sg, float& l, float& d) {
+  if constexpr (FORM == 0) {
+    l = fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+    d = gl_sigmoid(x) - t;
+  } else if constexpr (FORM == 1) {
+    l = (x - t) * (x - t);
+    d = 2.f * (x - t);
+  } else if constexpr (FORM == 2) {
+    l = sg * x;
+    d = sg;
+  } else if constexpr (FORM == 3) {
+    const float z = sg * x;
+    l = fmaxf(z, 0.f) + log1pf(expf(-fabsf(z)));
+    d = sg * gl_sigmoid(z);
+  } else {
+    const float z = 1.f + sg * x;
+    l = z > 0.f ? z : 0.f;
+    d = z > 0.f ? sg : 0.f;
+  }
+}
+
+// one streaming pass: grad (may be null) = dl/dx * gs in pred's dtype, one fp32 partial sum of l per block
+template <int FORM, typename PT>
+__global__ void __launch_bounds__(PL_THREADS)
+    gan_loss_kernel(const PT* __restrict__ pred, int64_t n, float t, float sg, float gs, PT* __restrict__ grad,
+                    float* __restrict__ partial, unsigned al) {
+  constexpr int V = Elt<PT>::PER16;
+  const int64_t nv = (n + V - 1) / V;
+  float s = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * PL_THREADS + threadIdx.x; i < nv; i += (int64_t)gridDim.x * PL_THREADS) {
+    const int64_t e0 = i * V;
+    const int cnt = n - e0 >= V ? V : (int)(n - e0);
+    const bool full = cnt == V;
+    float p[V], gv[V];
+    load_v<PT, V>(pred, e0, cnt, full && (al & AL_PRED), p);
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+      float l, d;
+      gan_term<FORM>(p[k], t, sg, l, d);
+      if (k < cnt) s += l;
+      gv[k] = d * gs;
+    }
+    if (grad) store_v<PT, V>(grad, e0, cnt, full && (al & AL_GRAD), gv);
+  }
+  block_sum_store(s, partial);
+}
+
+template <int FORM>
+void launch_gan(int dtype, unsigned grid, hipStream_t s, const void* pred, int64_t n, float t, float sg, float gs,
+                void* grad, float* partial, unsigned al) {
+  if (dtype == SR_BF16)
+    hipLaunchKernelGGL((gan_loss_kernel<FORM, bf16_t>), dim3(grid), dim3(PL_THREADS), 0, s, (const bf16_t*)pred, n, t, sg, gs,
+                       (bf16_t*)grad, partial, al);
+  else
+    hipLaunchKernelGGL((gan_loss_kernel<FORM, float>), dim3(grid), dim3(PL_THREADS), 0, s, (const float*)pred, n, t, sg, gs,
+                       (float*)grad, partial, al);
+}
+
 // blocks of a streaming pass over nv vectors: PL_BLOCKS_PER_CU per CU, fewer when the work is smaller
 unsigned loss_grid(int64_t nv) {
   int64_t g = (int64_t)sr_device_cus() * PL_BLOCKS_PER_CU;
@@ -317,6 +385,43 @@ int sr_pixel_loss(int kind, int reduction, int pred_dtype, int target_dtype, con
     hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(PL_THREADS), 0, s, (const float*)part_loss, (int)a.grid,
                        (double)loss_weight, denom, wmean ? (const double*)denom_dev : nullptr, loss);
   return sr_check(hipGetLastError(), "pixel_loss launch");
+}
+
+size_t sr_gan_loss_workspace(int64_t n) {
+  (void)n;
+  return PL_MAX_BLOCKS * sizeof(float);
+}
+
+int sr_gan_loss_block(int pred_dtype) { return PL_THREADS * (pred_dtype == SR_BF16 ? 8 : 4); }
+
+int sr_gan_loss(int kind, int pred_dtype, const void* pred, int64_t n, float target_val, int target_is_real, int is_disc,
+                float loss_weight, float* loss, void* grad, void* workspace, size_t ws_bytes, void* stream) {
+  if (!pred || !loss || !workspace || n <= 0) return sr_fail(SR_EINVAL, "gan_loss: bad arguments");
+  if (kind < SR_GAN_VANILLA || kind > SR_GAN_HINGE) return sr_fail(SR_EINVAL, "gan_loss: unknown kind");
+  if (pred_dtype != SR_F32 && pred_dtype != SR_BF16) return sr_fail(SR_EINVAL, "gan_loss: pred must be fp32 or bf16");
+  if (ws_bytes < sr_gan_loss_workspace(n)) return sr_fail(SR_EINVAL, "gan_loss: workspace too small");
+  const int psize = pred_dtype == SR_BF16 ? 2 : 4;
+  if ((((uintptr_t)pred | (uintptr_t)grad) & (psize - 1)) || (((uintptr_t)loss | (uintptr_t)workspace) & 3))
+    return sr_fail(SR_EINVAL, "gan_loss: tensors must be element-aligned");
+  if (n >= 0xffffffffll - 8) return sr_fail(SR_ETOOBIG, "gan_loss: tensor too large");
+  // loss_weight is for generators only (gan_loss.py:111-112)
+  const double lw = is_disc ? 1.0 : (double)loss_weight;
+  const float gs = (float)(lw / (double)n);
+  const float sg_real = target_is_real ? -1.f : 1.f;
+  const int V = 16 / psize;
+  const unsigned grid = loss_grid((n + V - 1) / V);
+  const unsigned al = (((uintptr_t)pred & 15) ? 0 : AL_PRED) | (((uintptr_t)grad & 15) ? 0 : AL_GRAD);
+  float* partial = (float*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  if (kind == SR_GAN_VANILLA) launch_gan<0>(pred_dtype, grid, s, pred, n, target_val, 0.f, gs, grad, partial, al);
+  else if (kind == SR_GAN_LSGAN) launch_gan<1>(pred_dtype, grid, s, pred, n, target_val, 0.f, gs, grad, partial, al);
+  else if (kind == SR_GAN_WGAN) launch_gan<2>(pred_dtype, grid, s, pred, n, 0.f, sg_real, gs, grad, partial, al);
+  else if (kind == SR_GAN_WGAN_SOFTPLUS) launch_gan<3>(pred_dtype, grid, s, pred, n, 0.f, sg_real, gs, grad, partial, al);
+  else if (is_disc) launch_gan<4>(pred_dtype, grid, s, pred, n, 0.f, sg_real, gs, grad, partial, al);
+  else launch_gan<2>(pred_dtype, grid, s, pred, n, 0.f, -1.f, gs, grad, partial, al);  // hinge generator: -mean(x)
+  hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(PL_THREADS), 0, s, (const float*)partial, (int)grid, lw, (double)n,
+                     (const double*)nullptr, loss);
+  return sr_check(hipGetLastError(), "gan_loss launch");
 }
 
 }  // extern "C"

@@ -3,8 +3,10 @@ from copy import deepcopy
 
 from ..utils.registry import LOSS_REGISTRY
 from .basic_loss import CharbonnierLoss, L1Loss, MSELoss, PerceptualLoss, WeightedTVLoss
+from .gan_loss import GANLoss, MultiScaleGANLoss
 
-__all__ = ['build_loss', 'L1Loss', 'MSELoss', 'CharbonnierLoss', 'WeightedTVLoss', 'PerceptualLoss']
+__all__ = ['build_loss', 'L1Loss', 'MSELoss', 'CharbonnierLoss', 'WeightedTVLoss', 'PerceptualLoss', 'GANLoss',
+           'MultiScaleGANLoss']
 
 
 def build_loss(opt):

@@ -50,9 +50,9 @@ class SRModel(BaseModel):
         if self.is_train:
             self.init_training_settings()
 
-    def init_training_settings(self):
+    def _init_amp_state(self, train_opt):
+        """``train.use_amp`` and the per-model step state; shared with the GAN models (models/srgan_model.py)."""
         self.net_g.train()
-        train_opt = self.opt['train']
         self.use_amp = bool(train_opt.get('use_amp', False))
         if self.use_amp:
             # the reference's AMP is fp16 autocast + GradScaler (basicsr/models/srrs_model.py:28-31,
@@ -61,6 +61,24 @@ class SRModel(BaseModel):
                                       '(the reference uses float16 + GradScaler; DESIGN.md §0)')
         self._graph = None
         self._eager_steps = 0
+
+    def _init_ema(self, train_opt):
+        """``train.ema_decay``: net_g_ema with a flat parameter vector of its own, from ``params_ema`` of
+        ``pretrain_network_g`` or a copy of net_g; shared with the GAN models."""
+        self.ema_decay = train_opt.get('ema_decay', 0)
+        if self.ema_decay > 0:
+            self.net_g_ema = build_network(self.opt['network_g']).to(self.device)
+            self.flat_ema = FlatParams(self.net_g_ema, with_grad=False)
+            load_path = self.opt.get('path', {}).get('pretrain_network_g', None)
+            if load_path is not None:
+                self.load_network(self.net_g_ema, load_path, self.opt['path'].get('strict_load_g', True), 'params_ema')
+            else:
+                self.model_ema(0)
+            self.net_g_ema.eval()
+
+    def init_training_settings(self):
+        train_opt = self.opt['train']
+        self._init_amp_state(train_opt)
         # HIP-graph capture of the train step (after 2 eager warm-up steps); distributed: a chain of
         # graphs cut at the gradient buckets, all-reduced between them (utils/step_graph.py)
         self.use_graph = bool(train_opt.get('cuda_graph', False))
@@ -81,16 +99,7 @@ class SRModel(BaseModel):
         # blocks whose side-stream launches share one fork (train.async_wgrad_blocks, ops.conv.side_batch;
         # SR_SIDE_BATCH overrides); applied only inside this model's backward (async_wgrad(blocks=))
         self.async_blocks = int(switch('SR_SIDE_BATCH') or train_opt.get('async_wgrad_blocks', 1))
-        self.ema_decay = train_opt.get('ema_decay', 0)
-        if self.ema_decay > 0:
-            self.net_g_ema = build_network(self.opt['network_g']).to(self.device)
-            self.flat_ema = FlatParams(self.net_g_ema, with_grad=False)
-            load_path = self.opt.get('path', {}).get('pretrain_network_g', None)
-            if load_path is not None:
-                self.load_network(self.net_g_ema, load_path, self.opt['path'].get('strict_load_g', True), 'params_ema')
-            else:
-                self.model_ema(0)
-            self.net_g_ema.eval()
+        self._init_ema(train_opt)
         self.cri_pix = self.build_optional_loss(train_opt, 'pixel_opt')
         self.cri_perceptual = self.build_optional_loss(train_opt, 'perceptual_opt')
         if self.cri_pix is None and self.cri_perceptual is None:
@@ -116,7 +125,7 @@ class SRModel(BaseModel):
     def _fused_step(self):
         return hasattr(self.optimizer_g, 'device_step')
 
-    def _perceptual_terms(self, l_total, loss_dict):
+    def _perceptual_terms(self, l_total, loss_dict, keys=('l_percep', 'l_style')):
         """l_percep / l_style of ``train.perceptual_opt`` (basicsr/models/sr_model.py:102-110) added to the
         total and the log; the VGG features are computed in the net's autocast mode (bf16 with use_amp)."""
         if not self.cri_perceptual:
@@ -125,10 +134,10 @@ class SRModel(BaseModel):
             l_percep, l_style = self.cri_perceptual(self.output, self.gt)
         if l_percep is not None:
             l_total = l_total + l_percep
-            loss_dict['l_percep'] = l_percep
+            loss_dict[keys[0]] = l_percep
         if l_style is not None:
             l_total = l_total + l_style
-            loss_dict['l_style'] = l_style
+            loss_dict[keys[1]] = l_style
         return l_total
 
     def _step_body(self, before_backward=None):

@@ -421,6 +421,77 @@ int sr_gram_fwd(int dtype, const void* F, int N, int HW, int C, float scale, flo
  * in fp32 (f32 MFMA for both dtypes). */
 int sr_gram_bwd(int dtype, const void* F, const float* dG, const void* res, int N, int HW, int C, float alpha,
                 float beta, void* dF, void* stream);
+/* ---------------------------------------------------------------------------------
+ * GAN training (csrc/gan.hip, csrc/loss.hip): the kernels of the VGGStyleDiscriminator
+ * (basicsr/archs/discriminator_arch.py) and the GANLoss (basicsr/losses/gan_loss.py).  Feature maps are dense
+ * NHWC of dtype (SR_F32 / SR_BF16), 16-byte aligned, channels padded to multiples of 8.  Fixed summation
+ * orders, no atomics; nothing allocates or synchronises; SR_EINVAL / SR_ETOOBIG before any launch.
+ *
+ * GAN loss of a prediction of n elements: *loss = w * mean(l(x)), grad (may be NULL, pred's dtype) =
+ * w * l'(x) / n, with w = loss_weight for a generator and 1 when is_disc.  vanilla: BCE with logits against
+ * target_val; lsgan: (x - target_val)^2; wgan: -x (real) / x (fake); wgan_softplus: softplus(-x) / softplus(x);
+ * hinge: relu(1 - x) / relu(1 + x) when is_disc, -x for a generator.  workspace: sr_gan_loss_workspace bytes,
+ * 4-byte aligned; sr_gan_loss_block: the elements one block of the streaming pass covers per trip.
+ * ------------------------------------------------------------------------------- */
+enum sr_gan_kind { SR_GAN_VANILLA = 0, SR_GAN_LSGAN = 1, SR_GAN_WGAN = 2, SR_GAN_WGAN_SOFTPLUS = 3, SR_GAN_HINGE = 4 };
+size_t sr_gan_loss_workspace(int64_t n);
+int sr_gan_loss_block(int pred_dtype);
+int sr_gan_loss(int kind, int pred_dtype, const void* pred, int64_t n, float target_val, int target_is_real, int is_disc,
+                float loss_weight, float* loss, void* grad, void* workspace, size_t ws_bytes, void* stream);
+/* nn.Conv2d(cin, cout, 4, 2, 1, bias=False) on x [N, H, W, Cin] -> y [N, H/2, W/2, Cout]; H, W even, Cin and
+ * Cout multiples of 8 from 8 to 512.  An implicit GEMM on MFMA bf16 16x16x32 / f32 16x16x4 with fp32 sums.
+ * prep: the GEMM images of the fp32 parameter w [cout_real][cin_real][4][4] in dtype: wf [Cout][16 * Cin] for
+ *   the forward, wd [4][Cin][4 * Cout] for the dgrad (one image per (row, column) parity of the input pixel);
+ *   padded channels are zeros.
+ * dgrad: dx [N, H, W, Cin] from dy [N, H/2, W/2, Cout]; every dx element is written once (a gather over the
+ *   four parity classes, 4 taps each).
+ * wgrad: dw [cout_real][cin_real][4][4] fp32 = (or += with accumulate) scale * the weight gradient; split K
+ *   over sr_conv4s2_wgrad_splits blocks of output pixels, fp32 partials in ws (sr_conv4s2_wgrad_workspace
+ *   bytes), summed in split order. */
+int sr_conv4s2_prep(int dtype, const float* w, int cout_real, int cin_real, int Cout, int Cin, void* wf, void* wd,
+                    void* stream);
+int sr_conv4s2_fwd(int dtype, const void* x, const void* wf, int N, int H, int W, int Cin, int Cout, void* y,
+                   void* stream);
+int sr_conv4s2_dgrad(int dtype, const void* dy, const void* wd, int N, int H, int W, int Cin, int Cout, void* dx,
+                     void* stream);
+size_t sr_conv4s2_wgrad_workspace(int N, int H, int W, int Cin, int Cout);
+int sr_conv4s2_wgrad_splits(int N, int H, int W, int Cin, int Cout);
+int sr_conv4s2_wgrad(int dtype, const void* dy, const void* x, int N, int H, int W, int Cin, int cin_real, int Cout,
+                     int cout_real, float scale, int accumulate, float* dw, void* ws, size_t ws_bytes, void* stream);
+/* BatchNorm2d over the M = N H W <= 2^24 rows of an NHWC map x [M][C] (C a multiple of 8 up to 1024), statistics and
+ * affine parameters fp32.  act: SR_ACT_NONE or SR_ACT_LRELU (fused after the affine).
+ * stats: save_mean, save_rstd = 1 / sqrt(biased variance + eps) by Welford updates per thread merged with
+ *   (count, mean, M2) partials in a fixed order over sr_bn_blocks(M) blocks (no E[x^2] - E[x]^2); with
+ *   running_mean / running_var (both or neither) also r = (1 - f) r + f * (mean | unbiased variance),
+ *   f = momentum, or 1 / *nbt (the already incremented num_batches_tracked, int64 on the device) when
+ *   momentum < 0.  M >= 2.  ws: sr_bn_workspace bytes.
+ * apply: y = act(gamma * (x - mean) * rstd + beta); rstd_or_var is save_rstd, or with use_var the running
+ *   variance (eval mode: rstd = 1 / sqrt(var + eps)).
+ * bwd_reduce: dbeta = sum g, dgamma = sum g * xhat, g = dy * act'(gamma * xhat + beta) recomputed from x.
+ * bwd_dx: dx = rstd * gamma * (g - dbeta / M - xhat * dgamma / M) when training, g * gamma * rstd otherwise. */
+size_t sr_bn_workspace(int64_t M, int C);
+int sr_bn_blocks(int64_t M);
+int sr_bn_stats(int dtype, const void* x, int64_t M, int C, float eps, float momentum, const int64_t* nbt, float* save_mean,
+                float* save_rstd, float* running_mean, float* running_var, void* ws, size_t ws_bytes, void* stream);
+int sr_bn_apply(int dtype, const void* x, int64_t M, int C, const float* mean, const float* rstd_or_var, int use_var,
+                float eps, const float* gamma, const float* beta, int act, float slope, void* y, void* stream);
+int sr_bn_bwd_reduce(int dtype, const void* x, const void* dy, int64_t M, int C, const float* mean,
+                     const float* rstd_or_var, int use_var, float eps, const float* gamma, const float* beta, int act,
+                     float slope, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream);
+int sr_bn_bwd_dx(int dtype, const void* x, const void* dy, int64_t M, int C, const float* mean, const float* rstd_or_var,
+                 int use_var, float eps, const float* gamma, const float* beta, int act, float slope,
+                 const float* dgamma, const float* dbeta, int training, void* dx, void* stream);
+/* Head linears on the fp32 nn.Linear parameters as they are: y fp32 [M][O] = act(x W^T + bias), x [M][K] of
+ * dtype, W [O][K].  P > 1: x's feature index is NHWC ((h w) * C + c, C = K / P) while W's is the NCHW flatten
+ * (c * P + (h w)); the kernels permute on the x side, so dw is in the parameter's order.  dgrad / wgrad take
+ * dy fp32 [M][O] and, with a fused LeakyReLU, the forward's output y (NULL: no activation); dx in dtype;
+ * dw / db = or += (accumulate), db may be NULL.  Sums in index order. */
+int sr_fc_fwd(int dtype, const void* x, const float* w, const float* bias, int M, int K, int O, int P, int act, float slope,
+              float* y, void* stream);
+int sr_fc_dgrad(int dtype, const float* dy, const float* y, const float* w, int M, int K, int O, int P, float slope,
+                void* dx, void* stream);
+int sr_fc_wgrad(int dtype, const float* dy, const float* y, const void* x, int M, int K, int O, int P, float slope,
+                int accumulate, float* dw, float* db, void* stream);
 /* Activation backward: out = alpha * dy * (y > 0 ? 1 : neg), neg = 0 for SR_ACT_RELU, slope for
  * SR_ACT_LRELU, 1 for SR_ACT_NONE; y is the activation OUTPUT (same sign as its input). */
 int sr_act_backward(int dtype, const void* dy, const void* y, int64_t n, int act, float slope, float alpha,
