@@ -60,10 +60,31 @@ SR_DEV void buf_store4f(__amdgpu_buffer_rsrc_t r, uint32_t off, float v) {
 
 // LayerNorm of a 192-channel token row held by 4 lanes (lane part has the 16-B chunks part, part + 4,
 // .., loaded into raw; chunks past KC are zero).  Padded channels of x are exactly zero (the NHWC
-// invariant), so the sum needs no mask; the 192 - C zero values add exactly mu^2 each to the squared
-// deviations, subtracted once after the row reduction (no per-element select).  Packed fp32 pairs.
+// invariant), so the sum needs no mask.  The squared deviations are summed over the real channels only:
+// step q of the four lanes covers channels 32 q .. 32 q + 31, so the steps below QS = C / 32 take every
+// value, the steps past it are skipped, and step QS, which straddles C, subtracts mu m with m = 1 on a real
+// channel and 0 on a pad (whose value is exactly 0, so its deviation is): one fma in place of the
+// subtraction, m computed ahead of the loads' arrival, one wave-uniform switch on QS.  (Summing the pads'
+// mu^2 and subtracting (192 - C) mu^2 afterwards cancelled on rows whose mean is large against their
+// spread: rstd off by 6400 u at C = 60, test_swin_fused_fp64_gpu.py.)  Packed fp32 pairs.
 SR_DEV f32x2 bf16x2_f(unsigned q) { return f32x2{__uint_as_float(q << 16), __uint_as_float(q & 0xffff0000u)}; }
-SR_DEV void ln_row4_stats(const u32x4 (&raw)[6], int C, float eps, float& mu, float& rs) {
+template <int QS>
+SR_DEV f32x2 ln_row4_sq(const u32x4 (&raw)[6], const f32x2 mu2, const f32x2 (&m2)[4]) {
+  f32x2 sq2 = {0.f, 0.f};
+#pragma unroll
+  for (int q = 0; q < 6 && q <= QS; ++q)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const f32x2 d = q < QS ? bf16x2_f(raw[q][j]) - mu2 : bf16x2_f(raw[q][j]) - mu2 * m2[j];
+      sq2 += d * d;
+    }
+  return sq2;
+}
+SR_DEV void ln_row4_stats(const u32x4 (&raw)[6], int part, int C, float eps, float& mu, float& rs) {
+  const int rem = (C & 31) - 8 * part;  // real channels of this lane's chunk in step C / 32 (<= 0: none)
+  f32x2 m2[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) m2[j] = f32x2{rem > 2 * j ? 1.f : 0.f, rem > 2 * j + 1 ? 1.f : 0.f};
   f32x2 sm2 = {0.f, 0.f};
 #pragma unroll
   for (int q = 0; q < 6; ++q)
@@ -73,19 +94,20 @@ SR_DEV void ln_row4_stats(const u32x4 (&raw)[6], int C, float eps, float& mu, fl
   sm += __shfl_xor(sm, 1);
   sm += __shfl_xor(sm, 2);
   mu = sm / C;
-  f32x2 sq2 = {0.f, 0.f};
   const f32x2 mu2 = {mu, mu};
-#pragma unroll
-  for (int q = 0; q < 6; ++q)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const f32x2 d = bf16x2_f(raw[q][j]) - mu2;
-      sq2 += d * d;
-    }
+  f32x2 sq2;
+  switch (C >> 5) {
+    case 0: sq2 = ln_row4_sq<0>(raw, mu2, m2); break;
+    case 1: sq2 = ln_row4_sq<1>(raw, mu2, m2); break;
+    case 2: sq2 = ln_row4_sq<2>(raw, mu2, m2); break;
+    case 3: sq2 = ln_row4_sq<3>(raw, mu2, m2); break;
+    case 4: sq2 = ln_row4_sq<4>(raw, mu2, m2); break;
+    case 5: sq2 = ln_row4_sq<5>(raw, mu2, m2); break;
+    default: sq2 = ln_row4_sq<6>(raw, mu2, m2); break;  // C = 192: every step whole
+  }
   float sq = sq2[0] + sq2[1];
   sq += __shfl_xor(sq, 1);
   sq += __shfl_xor(sq, 2);
-  sq = fmaxf(sq - (float)(192 - C) * mu * mu, 0.f);
   rs = rsqrtf(sq / C + eps);
 }
 // one normalised chunk (8 channels from c0): o = x A + B with A = rs gamma, B = beta - mu A (gamma /
@@ -300,7 +322,7 @@ __global__ __launch_bounds__(256 * NW, 3 - NW) void swin_attn_block_fwd_kernel(S
       sGB[192 + tid] = v_b;
     }
     float mu, rs;
-    ln_row4_stats(raw, a.C, a.eps, mu, rs);
+    ln_row4_stats(raw, part, a.C, a.eps, mu, rs);
     __syncthreads();  // gamma / beta staged
 #pragma unroll
     for (int q = 0; q < 6; ++q) {
@@ -665,7 +687,7 @@ __global__ __launch_bounds__(512, 1) void swin_mlp_block_fwd_kernel(SmbArgs a) {
       sGB[192 + tid] = v_b;
     }
     float mu, rs;
-    ln_row4_stats(raw, a.C, a.eps, mu, rs);
+    ln_row4_stats(raw, part, a.C, a.eps, mu, rs);
     __syncthreads();  // gamma / beta staged
 #pragma unroll
     for (int q = 0; q < 6; ++q) {
