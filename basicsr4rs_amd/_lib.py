@@ -81,6 +81,14 @@ class PrepItem(ctypes.Structure):
                 ('bias_g', _vp)]
 
 
+SN_MAX_PROBLEMS = 16  # SR_SN_MAX_PROBLEMS
+
+
+class SnProblem(ctypes.Structure):
+    _fields_ = [('w', _vp), ('u', _vp), ('v', _vp), ('u_fwd', _vp), ('v_fwd', _vp), ('sigma', _vp), ('out', _vp),
+                ('g', _vp), ('R', _i), ('K', _i)]
+
+
 class ConvKDesc(ctypes.Structure):
     _fields_ = [('dtype', _i), ('N', _i), ('H', _i), ('W', _i), ('k', _i), ('Cin', _i), ('Cin_real', _i), ('Cout', _i),
                 ('Cout_real', _i), ('act', _i), ('alpha', _f), ('scale', _f), ('accumulate', _i)]
@@ -152,6 +160,12 @@ SIGNATURES = {
     'sr_conv4s2_wgrad_workspace': (_sz, [_i, _i, _i, _i, _i]),
     'sr_conv4s2_wgrad_splits': (_i, [_i, _i, _i, _i, _i]),
     'sr_conv4s2_wgrad': (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _sz, _vp]),
+    'sr_conv4s2_fwd_act': (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    'sr_spectral_norm_workspace': (_sz, [ctypes.POINTER(SnProblem), _i]),
+    'sr_spectral_norm_fwd': (_i, [ctypes.POINTER(SnProblem), _i, _i, _f, _vp, _sz, _vp]),
+    'sr_spectral_norm_bwd': (_i, [ctypes.POINTER(SnProblem), _i, _i, _vp, _sz, _vp]),
+    'sr_bilinear_up2_fwd': (_i, [_i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'sr_bilinear_up2_bwd': (_i, [_i, _vp, _i, _i, _i, _i, _vp, _vp]),
     'sr_bn_workspace': (_sz, [_i64, _i]),
     'sr_bn_blocks': (_i, [_i64]),
     'sr_bn_stats': (_i, [_i, _vp, _i64, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -10,7 +10,8 @@
 //       and walks K in steps of 64: the pixel operand is GATHERED tap by tap (16 bytes = 8 bf16 / 4 fp32
 //       channels of one tap, zeros outside the map), the weight operand is a row of the image.  MFMA:
 //       v_mfma_f32_16x16x32_bf16 / v_mfma_f32_16x16x4_f32, fp32 accumulation, 4 waves = 2 x 2 of 32 x 32.
-//       Forward: pixel (n, oh, ow) reads x[2 oh - 1 + kh][2 ow - 1 + kw], K = 16 Cin.
+//       Forward: pixel (n, oh, ow) reads x[2 oh - 1 + kh][2 ow - 1 + kw], K = 16 Cin; an optional LeakyReLU on
+//       the fp32 sums before the store (sr_conv4s2_fwd_act: the U-Net discriminator, where no BatchNorm follows).
 //       Dgrad: ih = 2 oh - 1 + kh means an input row of parity ph meets only the two kh = 1 - ph + 2 th, from
 //       output rows oh = a + ph - th (ih = 2 a + ph); the same per column: each of the four parity classes
 //       (grid z) is a GEMM with K = 4 Cout over dy, written to its own pixels of dx.  Every dx element is
@@ -145,6 +146,8 @@ struct C4Args {
   int M;           // N * Hr * Wr
   int K, Nout;     // reduction length (taps * Cs) and output channels
   int Hd, Wd;      // the written map
+  int act;         // forward epilogue: 0 none, 2 LeakyReLU(slope)
+  float slope;
   FastDiv fd_w, fd_hw, fd_cs;
 };
 
@@ -227,6 +230,14 @@ __global__ void __launch_bounds__(G_THREADS)
   }
 
   // acc[i][j][r]: output channel n0 + wr * 32 + i * 16 + fq * 4 + r of pixel m0 + wc * 32 + j * 16 + fr
+  if (MODE == 0 && a.act == 2) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[i][j][r] = acc[i][j][r] > 0.f ? acc[i][j][r] : acc[i][j][r] * a.slope;
+  }
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int m = m0 + wc * 32 + j * 16 + fr;
@@ -739,18 +750,25 @@ int sr_conv4s2_prep(int dtype, const float* w, int cout_real, int cin_real, int 
   return sr_check(hipGetLastError(), "conv4s2_prep launch");
 }
 
-int sr_conv4s2_fwd(int dtype, const void* x, const void* wf, int N, int H, int W, int Cin, int Cout, void* y,
-                   void* stream) {
+int sr_conv4s2_fwd_act(int dtype, const void* x, const void* wf, int N, int H, int W, int Cin, int Cout, int act,
+                       float slope, void* y, void* stream) {
   if (!x || !wf || !y) return sr_fail(SR_EINVAL, "conv4s2_fwd: null pointer");
   if (int rc = c4_check("conv4s2_fwd", dtype, N, H, W, Cin, Cout)) return rc;
+  if (act != 0 && act != 2) return sr_fail(SR_EINVAL, "conv4s2_fwd: act must be none (0) or LeakyReLU (2)");
   if (((uintptr_t)x | (uintptr_t)wf | (uintptr_t)y) & 15) return sr_fail(SR_EINVAL, "conv4s2_fwd: tensors must be 16-byte aligned");
   C4Args a;
   a.Hs = H, a.Ws = W, a.Cs = Cin, a.Hr = H / 2, a.Wr = W / 2, a.M = N * a.Hr * a.Wr;
   a.K = 16 * Cin, a.Nout = Cout, a.Hd = a.Hr, a.Wd = a.Wr;
+  a.act = act, a.slope = slope;
   a.fd_w = make_fastdiv((uint32_t)a.Wr), a.fd_hw = make_fastdiv((uint32_t)(a.Hr * a.Wr)), a.fd_cs = make_fastdiv((uint32_t)Cin);
   if (dtype == SR_BF16) c4_launch<bf16_t, 0>(x, wf, y, a, 1, (hipStream_t)stream);
   else c4_launch<float, 0>(x, wf, y, a, 1, (hipStream_t)stream);
   return sr_check(hipGetLastError(), "conv4s2_fwd launch");
+}
+
+int sr_conv4s2_fwd(int dtype, const void* x, const void* wf, int N, int H, int W, int Cin, int Cout, void* y,
+                   void* stream) {
+  return sr_conv4s2_fwd_act(dtype, x, wf, N, H, W, Cin, Cout, 0, 0.f, y, stream);
 }
 
 int sr_conv4s2_dgrad(int dtype, const void* dy, const void* wd, int N, int H, int W, int Cin, int Cout, void* dx,
@@ -761,6 +779,7 @@ int sr_conv4s2_dgrad(int dtype, const void* dy, const void* wd, int N, int H, in
   C4Args a;
   a.Hs = H / 2, a.Ws = W / 2, a.Cs = Cout, a.Hr = H / 2, a.Wr = W / 2, a.M = N * a.Hr * a.Wr;
   a.K = 4 * Cout, a.Nout = Cin, a.Hd = H, a.Wd = W;
+  a.act = 0, a.slope = 0.f;
   a.fd_w = make_fastdiv((uint32_t)a.Wr), a.fd_hw = make_fastdiv((uint32_t)(a.Hr * a.Wr)), a.fd_cs = make_fastdiv((uint32_t)Cout);
   if (dtype == SR_BF16) c4_launch<bf16_t, 1>(dy, wd, dx, a, 4, (hipStream_t)stream);
   else c4_launch<float, 1>(dy, wd, dx, a, 4, (hipStream_t)stream);

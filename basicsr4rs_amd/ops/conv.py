@@ -684,28 +684,51 @@ def _images(weight, bias, spec, dtype, kp):
     return prepared_images(weight, bias, dtype, (spec.cout, spec.cin, kp[0], kp[1], spec.out_ps, 3))
 
 
+def fresh_images(weight, bias, spec, dtype):
+    """GEMM images (wf, wd, bias_g) of a 3x3 conv weight built for this call alone by one direct prep launch:
+    nothing is cached on the weight, registered in ``_PREP_ALL`` or retired from the batched-refresh table.  For
+    weights that are fresh tensors every forward (the spectral-normalised weights of ops/gan.py), which would
+    otherwise invalidate the generator's ``refresh_prepared`` table on every step."""
+    dev = weight.device
+    val = (torch.empty(spec.cout_p, 9 * spec.cin_p, device=dev, dtype=dtype),
+           torch.empty(spec.cin_p, 9 * spec.cout_p, device=dev, dtype=dtype),
+           torch.empty(spec.cout_p, device=dev, dtype=torch.float32))
+    lib = _lib.load()
+    w, b = weight.detach(), (bias.detach() if bias is not None else None)
+    args = (_lib.dtype_code(dtype), 3, _lib.ptr(w), _lib.ptr(b), spec.cout, spec.cin, spec.cout_p, spec.cin_p,
+            spec.out_ps, None, None, _lib.ptr(val[0]), _lib.ptr(val[1]), _lib.ptr(val[2]), _lib.stream())
+    with ktrace.span('conv_prep_kernel', 0.0, 4 * w.numel() + 2 * val[0].element_size() * val[0].numel(),
+                     relaunch=lambda a=args, k=(w, b, val): lib.sr_conv_prep_mapped(*a)):
+        _lib.check(lib.sr_conv_prep_mapped(*args))
+    return val
+
+
 class _Conv3x3(torch.autograd.Function):
-    """y = beta*res + alpha*act(conv3x3(x) + b), fused pixel-shuffle / NCHW-affine store."""
+    """y = beta*res + alpha*act(conv3x3(x) + b), fused pixel-shuffle / NCHW-affine store.  ``cache=False``: the
+    GEMM images are built for this call (fresh_images) and the dgrad's image is kept for the backward."""
 
     @staticmethod
-    def forward(ctx, x, res, weight, bias, spec):
+    def forward(ctx, x, res, weight, bias, spec, cache=True):
         dtype = x.dtype
         N, H, W = _grid(spec, x)
-        kp = _kpad(spec, dtype, H, W)
-        wf, wd, bg = _images(weight, bias, spec, dtype, kp)
+        kp = _kpad(spec, dtype, H, W) if cache else None
+        wf, wd, bg = _images(weight, bias, spec, dtype, kp) if cache else fresh_images(weight, bias, spec, dtype)
         out_dtype = torch.float32 if spec.out_nchw else dtype
         y = torch.empty(_out_shape(spec, N, H, W), device=x.device, dtype=out_dtype)
+        # with a residual behind the activation y's sign is no longer the gate's: keep the pre-activation
+        aux = torch.empty_like(y) if spec.act and res is not None else None
         conv_fwd_raw(x, wf, bg, y, N, H, W, kp[1] if kp else spec.cin_p, spec.cout_p, spec.cout, res=res,
                      aff_scale=spec.aff_scale, aff_shift=spec.aff_shift, act=spec.act, slope=spec.slope,
                      alpha=spec.alpha, beta=spec.beta, out_ps=spec.out_ps, out_nchw=spec.out_nchw,
-                     in_up=spec.in_up)
+                     in_up=spec.in_up, aux=aux)
         ctx.spec = spec
         # the dgrad stays on the unpadded images: the 158-KB kernel would wait for CUs the side-stream
         # weight gradients hold during backward (DESIGN note 38); the forward has the GPU to itself
         ctx.kp = None
         ctx.has_res = res is not None
         ctx.has_bias = bias is not None
-        ctx.save_for_backward(x, weight, bias, y if spec.act else None)
+        ctx.wd = None if cache else wd
+        ctx.save_for_backward(x, weight, bias, (aux if aux is not None else y) if spec.act else None)
         return y
 
     @staticmethod
@@ -727,7 +750,7 @@ class _Conv3x3(torch.autograd.Function):
             if spec.act:
                 dY = act_backward(dY, y, spec.act, spec.slope, alpha)
                 alpha = 1.0
-        _, wd, _ = _images(weight, bias, spec, dtype, ctx.kp)
+        wd = ctx.wd if ctx.wd is not None else _images(weight, bias, spec, dtype, ctx.kp)[1]
         dx = dres = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(N, H, W, spec.cin_p, device=x.device, dtype=dtype)
@@ -741,13 +764,14 @@ class _Conv3x3(torch.autograd.Function):
             dw, db = conv_wgrad_raw(dY, x, N, H, W, spec.cin_p, spec.cin, spec.cout_p, spec.cout, scale=alpha,
                                     out_ps=spec.out_ps, need_bias=ctx.has_bias, in_up=spec.in_up,
                                     params=(weight, bias))
-        return dx, dres, dw, db, None
+        return dx, dres, dw, db, None, None
 
 
-def conv3x3(x, conv, res=None, **kw):
-    """Apply an nn.Conv2d(., ., 3, 1, 1) parameter module to an NHWC feature map."""
+def conv3x3(x, conv, res=None, weight=None, cache=True, **kw):
+    """Apply an nn.Conv2d(., ., 3, 1, 1) parameter module to an NHWC feature map.  ``weight``: a tensor used in
+    place of ``conv.weight`` (same shape); with ``cache=False`` its GEMM images are built for this call alone."""
     spec = ConvSpec(conv.in_channels, conv.out_channels, **kw)
-    return _Conv3x3.apply(x, res, conv.weight, conv.bias, spec)
+    return _Conv3x3.apply(x, res, conv.weight if weight is None else weight, conv.bias, spec, cache)
 
 
 class _ConvChain(torch.autograd.Function):

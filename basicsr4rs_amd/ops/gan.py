@@ -1,10 +1,14 @@
-"""Ops of GAN training on the HIP kernels of csrc/gan.hip and csrc/loss.hip: the building blocks of the
-VGGStyleDiscriminator (basicsr/archs/discriminator_arch.py) and the GANLoss (basicsr/losses/gan_loss.py).
+"""Ops of GAN training on the HIP kernels of csrc/gan.hip, csrc/unet_disc.hip and csrc/loss.hip: the building
+blocks of the VGGStyleDiscriminator and the UNetDiscriminatorSN (basicsr/archs/discriminator_arch.py) and the GANLoss
+(basicsr/losses/gan_loss.py).
 
 ``conv4s2(x, conv)``: an ``nn.Conv2d(cin, cout, 4, 2, 1, bias=False)`` parameter module on an NHWC feature map.
 The GEMM images of the weight are cached on the parameter and rebuilt when its ``_version`` or the parameter
 epoch (ops/conv.py) changes; the weight gradient lands in the FlatParams gradient view through
 ``grad_target`` / ``grad_ready`` and is not launched for a weight that does not require grad.
+``conv4s2(x, conv, act, slope, weight)`` fuses a LeakyReLU and takes a weight override (per-call images).
+``spectral_norm_group(convs, training)``: every spectral-normalised weight of a net from one grouped launch sequence.
+``bilinear_up2(x)``: bilinear x2 (align_corners=False) of an NHWC map, forward and backward.
 ``batch_norm_act(x, bn, act, slope)``: ``nn.BatchNorm2d`` (affine, tracked running statistics) with an optional
 fused LeakyReLU, in the module's training or eval mode; statistics, gamma, beta and their gradients are fp32.
 ``linear(x, lin, act, slope, spatial)``: a head ``nn.Linear`` on its fp32 parameters; ``spatial`` = H * W of the
@@ -62,13 +66,33 @@ def conv4s2_images(weight, dtype):
     return val
 
 
-def conv4s2_fwd_raw(x, wf, cout_p):
+def conv4s2_fresh_images(weight, dtype):
+    """(wf, wd) built for this call alone by one prep launch, nothing cached on ``weight`` (a tensor that is new
+    every forward: a spectral-normalised weight)."""
+    cout, cin = weight.shape[:2]
+    cout_p, cin_p = C.pad8(cout), C.pad8(cin)
+    val = (torch.empty(cout_p, 16 * cin_p, device=weight.device, dtype=dtype),
+           torch.empty(4, cin_p, 4 * cout_p, device=weight.device, dtype=dtype))
+    lib = _lib.load()
+    w = weight.detach()
+    args = (_lib.dtype_code(dtype), _lib.ptr(w), cout, cin, cout_p, cin_p, _lib.ptr(val[0]), _lib.ptr(val[1]),
+            _lib.stream())
+    _launch('conv4s2_prep_kernel', 0.0, 4 * weight.numel() + val[0].element_size() * 2 * cout_p * 16 * cin_p,
+            lib.sr_conv4s2_prep, args, (w, val))
+    return val
+
+
+def conv4s2_fwd_raw(x, wf, cout_p, act=_lib.ACT_NONE, slope=0.0):
     N, H, W, cin_p = x.shape
     y = torch.empty(N, H // 2, W // 2, cout_p, device=x.device, dtype=x.dtype)
     lib = _lib.load()
-    args = (_lib.dtype_code(x.dtype), _lib.ptr(x), _lib.ptr(wf), N, H, W, cin_p, cout_p, _lib.ptr(y), _lib.stream())
+    head = (_lib.dtype_code(x.dtype), _lib.ptr(x), _lib.ptr(wf), N, H, W, cin_p, cout_p)
+    if act == _lib.ACT_NONE:
+        fn, args = lib.sr_conv4s2_fwd, head + (_lib.ptr(y), _lib.stream())
+    else:
+        fn, args = lib.sr_conv4s2_fwd_act, head + (act, float(slope), _lib.ptr(y), _lib.stream())
     _launch('conv4s2_fwd_kernel', 2.0 * y.numel() * 16 * cin_p, x.element_size() * (x.numel() + wf.numel() + y.numel()),
-            lib.sr_conv4s2_fwd, args, (x, wf, y))
+            fn, args, (x, wf, y))
     return y
 
 
@@ -119,39 +143,243 @@ def conv4s2_wgrad_raw(dy, x, cin, cout, scale=1.0, param=None):
 class _Conv4s2(torch.autograd.Function):
 
     @staticmethod
-    def forward(ctx, x, weight):
+    def forward(ctx, x, weight, act=_lib.ACT_NONE, slope=0.2, cache=True):
         cout = weight.shape[0]
-        wf, _ = conv4s2_images(weight, x.dtype)
-        ctx.save_for_backward(x, weight)
-        return conv4s2_fwd_raw(x, wf, C.pad8(cout))
+        wf, wd = conv4s2_images(weight, x.dtype) if cache else conv4s2_fresh_images(weight, x.dtype)
+        y = conv4s2_fwd_raw(x, wf, C.pad8(cout), act, slope)
+        ctx.cfg = (act, slope)
+        ctx.wd = None if cache else wd
+        ctx.save_for_backward(x, weight, y if act else None)
+        return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
+        x, weight, y = ctx.saved_tensors
+        act, slope = ctx.cfg
         cout, cin = weight.shape[:2]
         dY = dy.to(x.dtype).contiguous()
+        if act:
+            dY = C.act_backward(dY, y, act, slope, 1.0)
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            _, wd = conv4s2_images(weight, x.dtype)
+            wd = ctx.wd if ctx.wd is not None else conv4s2_images(weight, x.dtype)[1]
             dx = conv4s2_dgrad_raw(dY, wd, x.shape[1], x.shape[2], x.shape[3])
         if ctx.needs_input_grad[1]:
             dw = conv4s2_wgrad_raw(dY, x, cin, cout, param=weight)
-        return dx, dw
+        return dx, dw, None, None, None
 
 
-def conv4s2(x, conv):
+def conv4s2(x, conv, act=_lib.ACT_NONE, slope=0.2, weight=None):
     """Apply an nn.Conv2d(cin, cout, 4, 2, 1, bias=False) parameter module to an NHWC feature map
-    [N, H, W, pad8(cin)] with even H and W; returns [N, H / 2, W / 2, pad8(cout)]."""
+    [N, H, W, pad8(cin)] with even H and W; returns [N, H / 2, W / 2, pad8(cout)].  ``act``: ACT_NONE or a fused
+    LeakyReLU(slope).  ``weight``: a tensor used in place of ``conv.weight`` (a spectral-normalised weight); its
+    GEMM images are then built for this call alone and nothing is cached."""
     if (tuple(conv.kernel_size) != (4, 4) or tuple(conv.stride) != (2, 2) or tuple(conv.padding) != (1, 1)
             or tuple(conv.dilation) != (1, 1) or conv.groups != 1 or conv.bias is not None
             or conv.padding_mode != 'zeros'):
         raise ValueError(f'conv4s2: needs a 4 x 4 conv with stride 2, padding 1, no dilation, groups or bias; got {conv}')
+    if act not in (_lib.ACT_NONE, _lib.ACT_LRELU):
+        raise ValueError('conv4s2: act must be ACT_NONE or ACT_LRELU')
     _check_map(x, 'conv4s2', C.pad8(conv.in_channels))
     if x.shape[1] % 2 or x.shape[2] % 2 or x.shape[1] < 2 or x.shape[2] < 2:
         raise ValueError(f'conv4s2: H and W must be even and at least 2, got {tuple(x.shape)}')
     if C.pad8(conv.in_channels) > 512 or C.pad8(conv.out_channels) > 512:
         raise ValueError(f'conv4s2: at most 512 padded channels on either side, got {conv}')
-    return _Conv4s2.apply(x.contiguous(), conv.weight)
+    if weight is None:
+        return _Conv4s2.apply(x.contiguous(), conv.weight, act, slope, True)
+    if tuple(weight.shape) != (conv.out_channels, conv.in_channels, 4, 4) or weight.dtype != torch.float32:
+        raise ValueError(f'conv4s2: the weight override must be fp32 {(conv.out_channels, conv.in_channels, 4, 4)}')
+    return _Conv4s2.apply(x.contiguous(), weight.contiguous(), act, slope, False)
+
+
+# ------------------------------------------------------------------------------------------- spectral norm
+
+
+def _sn_layout(shapes):
+    """Offsets (in floats, multiples of 4) of W, u, v, sigma of every problem in one forward's state buffer."""
+    offs, o = [], 0
+    for R, K in shapes:
+        ow = o
+        ou = ow + (R * K + 3) // 4 * 4
+        ov = ou + (R + 3) // 4 * 4
+        osig = ov + (K + 3) // 4 * 4
+        o = osig + 4
+        offs.append((ow, ou, ov, osig))
+    return offs, o
+
+
+def _sn_call(fn_name, probs, extra, device):
+    """One grouped launch sequence per chunk of at most SN_MAX_PROBLEMS problems."""
+    lib = _lib.load()
+    fn = getattr(lib, fn_name)
+    calls = []
+    for c0 in range(0, len(probs), _lib.SN_MAX_PROBLEMS):
+        chunk = probs[c0:c0 + _lib.SN_MAX_PROBLEMS]
+        arr = (_lib.SnProblem * len(chunk))(*chunk)
+        ws_bytes = lib.sr_spectral_norm_workspace(arr, len(chunk))
+        ws = torch.empty(ws_bytes // 4, device=device, dtype=torch.float32)
+        calls.append((fn, (arr, len(chunk)) + extra + (_lib.ptr(ws), ws_bytes), ws))
+    return calls
+
+
+def _sn_problem(w, u, v, state, off, R, K, out=None, g=None):
+    p = _lib.SnProblem()
+    base = state.data_ptr()
+    p.w, p.u, p.v = w.data_ptr(), (u.data_ptr() if u is not None else None), (v.data_ptr() if v is not None else None)
+    p.u_fwd, p.v_fwd, p.sigma = base + 4 * off[1], base + 4 * off[2], base + 4 * off[3]
+    p.out = out.data_ptr() if out is not None else None
+    p.g = g.data_ptr() if g is not None else None
+    p.R, p.K = R, K
+    return p
+
+
+def spectral_norm_fwd_raw(weights, bufs, training, eps=1e-12):
+    """One grouped forward over fp32 ``weights`` [cout, ...] with ``bufs`` = [(u, v), ...] (updated in place when
+    ``training``).  Returns (outs, state, layout): the normalised weights (views of ``state``), this forward's state
+    buffer (W, u, v, sigma of every problem) and ``layout`` = (shapes, offsets) into it (``sn_state``)."""
+    shapes = [(w.shape[0], w[0].numel()) for w in weights]
+    offs, total = _sn_layout(shapes)
+    dev = weights[0].device
+    state = torch.empty(total, device=dev, dtype=torch.float32)
+    outs = [state[o[0]:o[0] + R * K].view(w.shape) for o, (R, K), w in zip(offs, shapes, weights)]
+    probs = [_sn_problem(w, u, v, state, o, R, K, out=out)
+             for w, (u, v), o, (R, K), out in zip(weights, bufs, offs, shapes, outs)]
+    n_el = sum(R * K for R, K in shapes)
+    keep = (weights, bufs, state)
+    for fn, args, ws in _sn_call('sr_spectral_norm_fwd', probs, (int(bool(training)), float(eps)), dev):
+        # w read by the column, row and scale passes (row and scale in eval), W written; the relaunch of a trace
+        # must not move u / v again, so a training call carries none
+        relaunch = None if training else (lambda a=args, k=(keep, ws), f=fn: f(*a, _lib.stream()))
+        with C.ktrace.span('spectral_norm_fwd_kernels', (5.0 if training else 3.0) * n_el,
+                           4.0 * n_el * (4 if training else 3), relaunch=relaunch, launches=5 if training else 4):
+            _lib.check(fn(*args, _lib.stream()))
+    return outs, state, (shapes, offs)
+
+
+def sn_state(state, layout, i):
+    """(W [R, K], u [R], v [K], sigma [1]) of problem i as views of a forward's state buffer."""
+    (R, K), (ow, ou, ov, osig) = layout[0][i], layout[1][i]
+    return state[ow:ow + R * K].view(R, K), state[ou:ou + R], state[ov:ov + K], state[osig:osig + 1]
+
+
+def spectral_norm_bwd_raw(state, layout, gs, outs, accumulate):
+    """One grouped backward: ``outs[i]`` (=, or += with ``accumulate``) (gs[i] - <gs[i], W> u v^T) / sigma with the
+    W, u, v, sigma of ``state``; problems whose ``gs[i]`` is None are skipped (their ``outs[i]`` may be None)."""
+    shapes, offs = layout
+    dev = state.device
+
+    def problems(targets):
+        return [_sn_problem(state[o[0]:], None, None, state, o, R, K, out=out, g=g)
+                for o, (R, K), out, g in zip(offs, shapes, targets, gs)]
+
+    n_el = sum(R * K for (R, K), g in zip(shapes, gs) if g is not None)
+    if n_el == 0:
+        return
+    calls = _sn_call('sr_spectral_norm_bwd', problems(outs), (int(bool(accumulate)), ), dev)
+    relaunches = [None] * len(calls)
+    if C.ktrace.active():  # the relaunch of a trace must not accumulate into the live gradient
+        scratch = [torch.empty_like(g) if g is not None else None for g in gs]
+        relaunches = [lambda a=args, k=(ws, scratch, gs, state), f=fn: f(*a, _lib.stream())
+                      for fn, args, ws in _sn_call('sr_spectral_norm_bwd', problems(scratch), (0, ), dev)]
+    for (fn, args, ws), rl in zip(calls, relaunches):
+        # G read by the dot and the apply pass, W by the dot, the target written (read too when accumulating)
+        with C.ktrace.span('spectral_norm_bwd_kernels', 6.0 * n_el, 4.0 * n_el * (5 if accumulate else 4), relaunch=rl,
+                           launches=2):
+            _lib.check(fn(*args, _lib.stream()))
+
+
+class _SpectralNormGroup(torch.autograd.Function):
+    """All spectral-normalised weights of a network from one grouped launch sequence."""
+
+    @staticmethod
+    def forward(ctx, training, eps, bufs, *weights):
+        ctx.set_materialize_grads(False)
+        outs, state, ctx.layout = spectral_norm_fwd_raw([w.detach() for w in weights], bufs, training, eps)
+        ctx.save_for_backward(state, *weights)
+        ctx.mark_non_differentiable(*[o for o, w in zip(outs, weights) if not w.requires_grad])
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        state, *weights = ctx.saved_tensors
+        none = (None, None, None)
+        need = [ctx.needs_input_grad[3 + i] and grads[i] is not None for i in range(len(weights))]
+        if not any(need):
+            return none + (None, ) * len(weights)
+        gs = [g.float().contiguous() if nd else None for g, nd in zip(grads, need)]
+        targets = [C.grad_target(w) if nd else None for w, nd in zip(weights, need)]
+        direct = all(t is not None for t, nd in zip(targets, need) if nd)
+        if not direct:
+            targets = [torch.empty_like(g) if g is not None else None for g in gs]
+        spectral_norm_bwd_raw(state, ctx.layout, gs, targets, direct)
+        if not direct:
+            return none + tuple(targets)
+        for w, nd in zip(weights, need):
+            if nd:
+                C.grad_ready(w)
+        return none + (None, ) * len(weights)
+
+
+def spectral_norm_group(convs, training, eps=1e-12):
+    """The spectral-normalised weights of ``convs`` (modules wrapped by ``torch.nn.utils.spectral_norm``: parameter
+    ``weight_orig``, buffers ``weight_u`` / ``weight_v``), all from ONE grouped launch sequence whose length does not
+    depend on ``len(convs)``.  ``training``: run the power iteration (one step, ``weight_u`` / ``weight_v`` updated in
+    place, also under ``no_grad`` and with frozen parameters); else sigma comes from the stored vectors.  The modules
+    themselves are never called.  Returns fresh fp32 tensors in the ``nn.Conv2d`` layout; the backward takes the
+    convs' weight gradients G, launches nothing for a frozen ``weight_orig`` (nothing at all when every one is), and
+    accumulates (G - <G, W> u v^T) / sigma with the u, v, sigma, W of ITS OWN forward straight into the FlatParams
+    gradient views."""
+    weights = [m.weight_orig for m in convs]
+    bufs = [(m.weight_u, m.weight_v) for m in convs]
+    for w, (u, v) in zip(weights, bufs):
+        if not (w.is_cuda and u.is_cuda and v.is_cuda):
+            raise NotImplementedError(_CPU_MESSAGE)
+        if w.dtype != torch.float32 or not w.is_contiguous() or u.numel() != w.shape[0] or v.numel() != w[0].numel():
+            raise ValueError('spectral_norm_group: weight_orig must be contiguous fp32 with weight_u [cout] and '
+                             'weight_v [cin * kh * kw]')
+    return _SpectralNormGroup.apply(bool(training), eps, bufs, *weights)
+
+
+# --------------------------------------------------------------------------------------------- bilinear x2
+
+
+def bilinear_up2_fwd_raw(x):
+    N, H, W, Cc = x.shape
+    y = torch.empty(N, 2 * H, 2 * W, Cc, device=x.device, dtype=x.dtype)
+    lib = _lib.load()
+    args = (_lib.dtype_code(x.dtype), _lib.ptr(x), N, H, W, Cc, _lib.ptr(y), _lib.stream())
+    # 4 taps per output element; x read once (each element 4 times, from cache), y written
+    _launch('up2_fwd_kernel', 7.0 * y.numel(), x.element_size() * (x.numel() + y.numel()), lib.sr_bilinear_up2_fwd, args,
+            (x, y))
+    return y
+
+
+def bilinear_up2_bwd_raw(dy):
+    N, H2, W2, Cc = dy.shape
+    dx = torch.empty(N, H2 // 2, W2 // 2, Cc, device=dy.device, dtype=dy.dtype)
+    lib = _lib.load()
+    args = (_lib.dtype_code(dy.dtype), _lib.ptr(dy), N, H2 // 2, W2 // 2, Cc, _lib.ptr(dx), _lib.stream())
+    _launch('up2_bwd_kernel', 7.0 * dy.numel(), dy.element_size() * (dx.numel() + dy.numel()), lib.sr_bilinear_up2_bwd,
+            args, (dy, dx))
+    return dx
+
+
+class _BilinearUp2(torch.autograd.Function):
+
+    @staticmethod
+    def forward(ctx, x):
+        return bilinear_up2_fwd_raw(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return bilinear_up2_bwd_raw(dy.contiguous())
+
+
+def bilinear_up2(x):
+    """``F.interpolate(scale_factor=2, mode='bilinear', align_corners=False)`` of an NHWC feature map
+    [N, H, W, C] (C a multiple of 8, fp32 or bf16) -> [N, 2H, 2W, C], with its backward (a gather, no atomics)."""
+    _check_map(x, 'bilinear_up2')
+    return _BilinearUp2.apply(x.contiguous())
 
 
 # ---------------------------------------------------------------------------------------------- batch norm

@@ -458,6 +458,43 @@ size_t sr_conv4s2_wgrad_workspace(int N, int H, int W, int Cin, int Cout);
 int sr_conv4s2_wgrad_splits(int N, int H, int W, int Cin, int Cout);
 int sr_conv4s2_wgrad(int dtype, const void* dy, const void* x, int N, int H, int W, int Cin, int cin_real, int Cout,
                      int cout_real, float scale, int accumulate, float* dw, void* ws, size_t ws_bytes, void* stream);
+/* sr_conv4s2_fwd with an activation epilogue: y = act(conv), act SR_ACT_NONE (the bits of sr_conv4s2_fwd) or
+ * SR_ACT_LRELU with slope.  The backward applies sr_act_backward to dy, then the dgrad / wgrad above. */
+int sr_conv4s2_fwd_act(int dtype, const void* x, const void* wf, int N, int H, int W, int Cin, int Cout, int act,
+                       float slope, void* y, void* stream);
+/* Spectral normalisation of conv weights (torch.nn.utils.spectral_norm: one power iteration, fp32 throughout),
+ * GROUPED: one call serves n <= SR_SN_MAX_PROBLEMS matrices M = w [R][K] (R = cout, K = cin kh kw, R K < 2^30), so the
+ * launch count does not depend on n.  The table is read on the host and travels to the kernels in their argument
+ * segment: nothing is uploaded and it need not outlive the call.
+ * fwd, iterate != 0: t = M^T u, v = t / max(|t|, eps), s = M v, u = s / max(|s|, eps), sigma = u . s; u and v are
+ *   updated in place and also copied to u_fwd / v_fwd (what this forward's backward reads); out = w / sigma.
+ *   iterate == 0 (eval): u, v untouched, u_fwd / v_fwd their copies, sigma = u . (M v).
+ * bwd: w = the normalised weight the forward wrote, g = dL/dW or NULL (the problem is skipped; with no g at all
+ *   nothing is launched); out [R][K] (=, or += with accumulate) (g - <g, w> u_fwd v_fwd^T) / sigma.
+ * Fixed summation orders, no atomics.  16-byte accesses where K % 4 == 0 and w, v_fwd, out, g are 16-byte
+ * aligned, scalar ones otherwise.  ws: sr_spectral_norm_workspace(problems, n) bytes, 16-byte aligned. */
+#define SR_SN_MAX_PROBLEMS 16
+typedef struct sr_sn_problem {
+  const float* w;
+  float* u;
+  float* v;
+  float* u_fwd;
+  float* v_fwd;
+  float* sigma;
+  float* out;
+  const float* g;
+  int R, K;
+} sr_sn_problem;
+size_t sr_spectral_norm_workspace(const sr_sn_problem* problems, int n);
+int sr_spectral_norm_fwd(const sr_sn_problem* problems, int n, int iterate, float eps, void* ws, size_t ws_bytes,
+                         void* stream);
+int sr_spectral_norm_bwd(const sr_sn_problem* problems, int n, int accumulate, void* ws, size_t ws_bytes, void* stream);
+/* Bilinear x2 upsampling (align_corners=False) of an NHWC map x [N, H, W, C] -> y [N, 2H, 2W, C], C a multiple of
+ * 8, fp32 or bf16, 16-byte accesses (misaligned pointers are refused), fp32 arithmetic and one rounding on store.
+ * Per axis out[2i] = .25 in[max(i-1, 0)] + .75 in[i], out[2i+1] = .75 in[i] + .25 in[min(i+1, n-1)].
+ * bwd: dx [N, H, W, C] from dy [N, 2H, 2W, C], the transpose as a gather (every dx element written once). */
+int sr_bilinear_up2_fwd(int dtype, const void* x, int N, int H, int W, int C, void* y, void* stream);
+int sr_bilinear_up2_bwd(int dtype, const void* dy, int N, int H, int W, int C, void* dx, void* stream);
 /* BatchNorm2d over the M = N H W <= 2^24 rows of an NHWC map x [M][C] (C a multiple of 8 up to 1024), statistics and
  * affine parameters fp32.  act: SR_ACT_NONE or SR_ACT_LRELU (fused after the affine).
  * stats: save_mean, save_rstd = 1 / sqrt(biased variance + eps) by Welford updates per thread merged with

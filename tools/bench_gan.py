@@ -8,6 +8,10 @@ alternating call by call.  One JSON line per case:
 
     python tools/bench_gan.py [--calls 20] [--warmup 5] [--batch 16] [--no-step]
 
+``--disc unet`` times the UNetDiscriminatorSN instead (num_feat 64, batch 12 at 256^2, the geometry of
+options/train/RealESRGAN/train_realesrgan_x4plus.yml) against stock PyTorch with torch's ``spectral_norm`` and
+``F.interpolate``, both in training mode, by the same method; no train step is timed for it.
+
 ``--trace`` prints instead, per dtype, the ``ktrace`` event spans of one discriminator forward + backward (after two
 untraced ones): per kernel name the launches, the summed milliseconds and the algorithmic TFLOP/s and GB/s.
 """
@@ -48,6 +52,30 @@ class StockDiscriminator(nn.Module):
         return self.linear2(F.leaky_relu(self.linear1(h.flatten(1)), 0.2))
 
 
+class StockUNetSN(nn.Module):
+    """The UNetDiscriminatorSN layer list in nn modules with torch's spectral_norm (run in channels_last)."""
+
+    def __init__(self, num_in_ch=3, nf=64):
+        super().__init__()
+        norm = nn.utils.spectral_norm
+        self.conv0 = nn.Conv2d(num_in_ch, nf, 3, 1, 1)
+        self.down = nn.ModuleList(norm(nn.Conv2d(nf * m, nf * m * 2, 4, 2, 1, bias=False)) for m in (1, 2, 4))
+        self.up = nn.ModuleList(norm(nn.Conv2d(nf * m * 2, nf * m, 3, 1, 1, bias=False)) for m in (4, 2, 1))
+        self.conv7 = norm(nn.Conv2d(nf, nf, 3, 1, 1, bias=False))
+        self.conv8 = norm(nn.Conv2d(nf, nf, 3, 1, 1, bias=False))
+        self.conv9 = nn.Conv2d(nf, 1, 3, 1, 1)
+
+    def forward(self, x):
+        act = lambda t: F.leaky_relu(t, 0.2)  # noqa: E731
+        xs = [act(self.conv0(x))]
+        for c in self.down:
+            xs.append(act(c(xs[-1])))
+        h = xs.pop()
+        for c in self.up:
+            h = act(c(F.interpolate(h, scale_factor=2, mode='bilinear', align_corners=False))) + xs.pop()
+        return self.conv9(act(self.conv8(act(self.conv7(h)))))
+
+
 def timed(fns, calls, warmup):
     ms = [[] for _ in fns]
     for i in range(warmup + calls):
@@ -86,17 +114,24 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--calls', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--batch', type=int, default=16)
+    ap.add_argument('--batch', type=int, default=None, help='default 16 (--disc vgg) or 12 (--disc unet)')
+    ap.add_argument('--disc', choices=['vgg', 'unet'], default='vgg')
     ap.add_argument('--no-step', action='store_true')
     ap.add_argument('--trace', action='store_true')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('bench_gan.py needs the GPU')
     torch.manual_seed(0)
-    B = args.batch
-    hip = build_network(dict(type='VGGStyleDiscriminator', num_in_ch=3, num_feat=64, input_size=128)).cuda()
-    stock = StockDiscriminator().cuda().to(memory_format=torch.channels_last)
-    x = torch.rand(B, 3, 128, 128, device='cuda')
+    unet = args.disc == 'unet'
+    B = args.batch or (12 if unet else 16)
+    if unet:
+        hip = build_network(dict(type='UNetDiscriminatorSN', num_in_ch=3, num_feat=64, skip_connection=True)).cuda()
+        stock = StockUNetSN().cuda().to(memory_format=torch.channels_last)
+        x = torch.rand(B, 3, 256, 256, device='cuda')
+    else:
+        hip = build_network(dict(type='VGGStyleDiscriminator', num_in_ch=3, num_feat=64, input_size=128)).cuda()
+        stock = StockDiscriminator().cuda().to(memory_format=torch.channels_last)
+        x = torch.rand(B, 3, 128, 128, device='cuda')
     if args.trace:
         trace(hip, x)
         return
@@ -116,10 +151,11 @@ def main():
 
         (h_med, h_min), (s_med, s_min) = timed([run(hip, x), run(stock, x.contiguous(memory_format=torch.channels_last))],
                                                args.calls, args.warmup)
-        print(json.dumps(dict(case='discriminator fwd+bwd', batch=B, dtype='bf16' if amp else 'fp32',
+        print(json.dumps(dict(case='UNetDiscriminatorSN fwd+bwd' if unet else 'discriminator fwd+bwd', batch=B,
+                              dtype='bf16' if amp else 'fp32',
                               hip_ms=round(h_med, 3), hip_min_ms=round(h_min, 3), torch_ms=round(s_med, 3),
                               torch_min_ms=round(s_min, 3))), flush=True)
-    if args.no_step:
+    if args.no_step or unet:
         return
     for amp in (True, False):
         opt = dict(model_type='ESRGANModel', is_train=True, dist=False, num_gpu=1, path={},
