@@ -137,8 +137,7 @@ int wg_row3_bg();
 int ring_ct(const sr_conv3x3_wgrad_desc* d);
 int ring_tiles_co(const sr_conv3x3_wgrad_desc* d);
 
-// Launchers, each defined in the file of its kernels (conv3x3.hip for the families that have no file of their
-// own yet: the file names below are where they are going).  The weight-gradient launchers take the arguments with the
+// Launchers, each defined in the file of its kernels.  The weight-gradient launchers take the arguments with the
 // split plan filled in (splits, kper, taps) and set the tile counts of their kernel.
 hipError_t launch_fwd_tile(const FwdArgs& a, FwdKind k, bool bf16, hipStream_t s);  // conv3x3_fwd_tile.hip
 hipError_t launch_fwd_big(const FwdArgs& a0, hipStream_t s);                         // conv3x3_fwd_pp.hip

@@ -1,6 +1,6 @@
 // conv3x3 forward / dgrad for narrow convs, row-streaming persistent form: conv3x3_fwd_band_kernel and its
 // launches (whole rows, 128-px column strips).  "The tile kernel above" of the comment below is
-// conv3x3_fwd_halo_kernel (conv3x3.hip).
+// conv3x3_fwd_halo_kernel (conv3x3_fwd_tile.hip).
 #include "conv3x3_args.h"
 #include "conv3x3_dev.h"
 

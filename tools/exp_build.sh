@@ -1,8 +1,8 @@
 #!/bin/bash
 # Experimental build of libsr_hip.so: one source recompiled with extra flags, linked with the other objects
 # of the current build -> abl/lib<tag>.so (A/B only; never the shipped library).
-# The source is $SRC: conv3x3 (the conv dispatch and the kernels not yet in a family file) by default; for a
-# kernel in a family file name that file, e.g. SRC=conv3x3_fwd_band (conv3x3.hip's header comment has the map).
+# The source is $SRC: conv3x3 (the conv selection and dispatch, host code only) by default; for a kernel name
+# its family file, e.g. SRC=conv3x3_fwd_band (conv3x3.hip's header comment has the map).
 # usage: [SRC=<file without .hip>] bash tools/exp_build.sh <tag> "<flags>"
 set -e
 cd "$(dirname "$0")/../basicsr4rs_amd/csrc"
