@@ -236,6 +236,16 @@ SIGNATURES = {
     'sr_fused_lrelu_bwd': (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i64, _f, _f, _vp, _sz, _vp]),
     'sr_upfirdn2d_out_size': (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'sr_upfirdn2d': (_i, [_i, _vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    'sr_filter2d': (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp]),
+    'sr_sep_blur': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    'sr_usm_sharp_launches': (_i, []),
+    'sr_usm_sharp': (_i, [_vp, _i, _i, _i, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    'sr_resize': (_i, [_vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp]),
+    'sr_gaussian_apply': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'sr_level_presence': (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    'sr_poisson_rate': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'sr_poisson_apply': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'sr_jpeg': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
 }
 
 _LIB = None

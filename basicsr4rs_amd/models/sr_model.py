@@ -125,13 +125,14 @@ class SRModel(BaseModel):
     def _fused_step(self):
         return hasattr(self.optimizer_g, 'device_step')
 
-    def _perceptual_terms(self, l_total, loss_dict, keys=('l_percep', 'l_style')):
+    def _perceptual_terms(self, l_total, loss_dict, keys=('l_percep', 'l_style'), gt=None):
         """l_percep / l_style of ``train.perceptual_opt`` (basicsr/models/sr_model.py:102-110) added to the
-        total and the log; the VGG features are computed in the net's autocast mode (bf16 with use_amp)."""
+        total and the log; the VGG features are computed in the net's autocast mode (bf16 with use_amp).
+        ``gt``: the target in place of ``self.gt`` (the Real-ESRGAN models' sharpened ground truth)."""
         if not self.cri_perceptual:
             return l_total
         with torch.autocast('cuda', dtype=torch.bfloat16, enabled=self.use_amp):
-            l_percep, l_style = self.cri_perceptual(self.output, self.gt)
+            l_percep, l_style = self.cri_perceptual(self.output, self.gt if gt is None else gt)
         if l_percep is not None:
             l_total = l_total + l_percep
             loss_dict[keys[0]] = l_percep

@@ -93,23 +93,25 @@ class SRGANModel(SRModel):
     def _update_g(self, current_iter):
         return current_iter % self.net_d_iters == 0 and current_iter > self.net_d_init_iters
 
-    def _g_content_terms(self, loss_dict):
-        """Pixel and perceptual / style terms of the generator loss and their log entries."""
+    def _g_content_terms(self, loss_dict, pix_gt=None, percep_gt=None):
+        """Pixel and perceptual / style terms of the generator loss and their log entries.  ``pix_gt`` /
+        ``percep_gt``: the targets in place of ``self.gt`` (models/realesrgan_model.py)."""
         l_g_total = 0
         if self.cri_pix:
-            l_g_pix = self.cri_pix(self.output, self.gt)
+            l_g_pix = self.cri_pix(self.output, self.gt if pix_gt is None else pix_gt)
             l_g_total = l_g_total + l_g_pix
             loss_dict['l_g_pix'] = l_g_pix
-        l_g_total = self._perceptual_terms(l_g_total, loss_dict, keys=('l_g_percep', 'l_g_style'))
+        l_g_total = self._perceptual_terms(l_g_total, loss_dict, keys=('l_g_percep', 'l_g_style'), gt=percep_gt)
         return l_g_total
 
     def _g_gan_term(self):
         fake_g_pred = self._d(self.output)
         return self.cri_gan(fake_g_pred, True, is_disc=False)
 
-    def _d_terms(self, loss_dict):
-        """The discriminator half: both backwards of the reference, in its order."""
-        real_d_pred = self._d(self.gt)
+    def _d_terms(self, loss_dict, real=None):
+        """The discriminator half: both backwards of the reference, in its order.  ``real``: the real sample in
+        place of ``self.gt``."""
+        real_d_pred = self._d(self.gt if real is None else real)
         l_d_real = self.cri_gan(real_d_pred, True, is_disc=True)
         loss_dict['l_d_real'] = l_d_real
         loss_dict['out_d_real'] = torch.mean(real_d_pred.detach())

@@ -808,6 +808,58 @@ int sr_upfirdn2d(int dtype, const void* x, int major, int in_h, int in_w, const 
                  int up_x, int up_y, int down_x, int down_y, int pad_x0, int pad_x1, int pad_y0, int pad_y1,
                  void* out, void* stream);
 
+/* The Real-ESRGAN degradation pipeline on the device (csrc/degrade.hip; basicsr/models/realesrgan_model.py:68-185).
+ * Images are contiguous NCHW fp32; every pointer 4-byte aligned (16-byte vector stores are chosen where the
+ * pointer and the row length allow, never required); tensors below 2^31 elements; no fp atomics.
+ * round255 != 0 stores clamp(rint(255 v), 0, 255) / 255 (a true division) in place of v. */
+
+/* filter2D (img_process_util.py:7-31): reflect-padded correlation of every plane of sample n with
+ * kernel[n] ([B][k][k], kernel_batch != 0) or kernel[0] ([1][k][k]); k odd, 3..21; k / 2 < min(H, W);
+ * y must not be x. */
+int sr_filter2d(const float* x, int B, int C, int H, int W, const float* kernel, int kernel_batch, int k, int round255,
+                float* y, void* stream);
+/* Separable blur: y = the r-tap filter `taps` along rows, then along columns, each reflect-padded by r / 2
+ * (r odd <= 51, r / 2 < min(H, W)); tmp (planes H W floats) holds the row pass.  Two launches. */
+int sr_sep_blur(const float* x, int planes, int H, int W, const float* taps, int r, float* tmp, float* y,
+                void* stream);
+/* USMSharp.forward (img_process_util.py:74-83) with the separable blur: residual = x - blur(x) and
+ * mask = |residual| * 255 > threshold (both written, planes H W floats each), soft = blur(mask),
+ * y = soft * clip(x + weight * residual, 0, 1) + (1 - soft) * x.  sr_usm_sharp_launches() kernel launches:
+ * row, column + residual / mask, row, column + blend. */
+int sr_usm_sharp_launches(void);
+int sr_usm_sharp(const float* x, int planes, int H, int W, const float* taps, int r, float weight, float threshold,
+                 float* tmp, float* residual, float* mask, float* y, void* stream);
+/* F.interpolate(align_corners=False, antialias=False) to Hout x Wout; mode 0 area (adaptive average,
+ * integer windows), 1 bilinear, 2 bicubic (A = -0.75, clamped indices, not clamped values).  scale_h / scale_w:
+ * the source-coordinate scales, 1 / scale_factor when torch is given a scale_factor, in / out when it is given
+ * a size (ignored by area). */
+int sr_resize(const float* x, int planes, int Hin, int Win, int Hout, int Wout, int mode, float scale_h, float scale_w,
+              float* y, void* stream);
+/* add_gaussian_noise_pt (degradations.py:460-511) with the draws given: out = clamp(img + (normal sigma_n / 255)
+ * (1 - gray_n) + (normal_gray sigma_n / 255) gray_n, 0, 1); img, normal [B][3][H][W], normal_gray [H][W] shared
+ * by the batch, sigma, gray [B]; normal_gray and gray both NULL: colour noise only.  finish (both noise entries):
+ * flags 1 = round to 8 bits (rint(255 v) / 255), 2 = no clip, 4 = store the noise alone, without the image. */
+int sr_gaussian_apply(const float* img, const float* normal, const float* normal_gray, const float* sigma,
+                      const float* gray, int B, int H, int W, int finish, float* out, void* stream);
+/* generate_poisson_noise_pt (degradations.py:609-654) without the host: sr_level_presence ORs the 8-bit levels
+ * clamp(rint(255 v), 0, 255) present in sample n into bitmap[n][0][8] (the three channels) and bitmap[n][1][8]
+ * (the gray image 0.2989 r + 0.587 g + 0.114 b); the caller zeroes bitmap ([B][2][8] 32-bit words) first.
+ * sr_poisson_rate: vals[n][c] = 2^ceil(log2(levels present)), rate_c [B][3][H][W] = level / 255 * vals[n][0],
+ * rate_g [B][H][W] likewise for gray.  sr_poisson_apply: out = clamp(img + ((draw_c / vals_c - level / 255)
+ * (1 - gray_n) + (draw_g / vals_g - gray level / 255) gray_n) scale_n, 0, 1); draw_g and gray both NULL:
+ * colour noise only. */
+int sr_level_presence(const float* img, int B, int H, int W, unsigned* bitmap, void* stream);
+int sr_poisson_rate(const float* img, const unsigned* bitmap, int B, int H, int W, float* rate_c, float* rate_g,
+                    float* vals, void* stream);
+int sr_poisson_apply(const float* img, const float* draw_c, const float* draw_g, const float* vals, const float* scale,
+                     const float* gray, int B, int H, int W, int finish, float* out, void* stream);
+/* DiffJPEG.forward (diffjpeg.py:449-491) of x [B][3][H][W] in [0, 1] at quality[n] ([B], read only): zero pad
+ * to multiples of 16, x 255, YCbCr, 2 x 2 chroma mean, 8 x 8 DCT, / (table factor_n), rint (differentiable != 0:
+ * r + (v - r)^3), and back; y = clamp(., 0, 255) / 255 cropped to H x W.  coef (may be NULL): the quantised
+ * coefficients, Y [B][H16/8][W16/8][8][8] followed by Cb and Cr [B][H16/16][W16/16][8][8] each. */
+int sr_jpeg(const float* x, int B, int H, int W, const float* quality, int differentiable, int round255, float* y,
+            float* coef, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
