@@ -24,6 +24,7 @@
 #include "sr_common.h"
 #include "sr_internal.h"
 
+#include <algorithm>
 #include <cstdlib>
 
 namespace {
@@ -1181,9 +1182,12 @@ __global__ void __launch_bounds__(DC8_NT, 2) dcn_coord_dy8_kernel(DcnArgs a, con
 }
 
 // The scatter kernel.  FXB 64: the int64 fixed-point LDS image of the
-// round-3 kernel (scale 2^(48 - e) for a per-image max |mask * dcols| below 2^e); FXB 32: int32 fixed
-// point, scale 2^(18 - e): a cell sums at most 16 x 16 pixels x 9 taps < 2^12 contributions of at
-// most 2^18 each, so it cannot overflow; the quantum is 2^-18 of the image's max |mask * dcols| (the
+// round-3 kernel (scale 2^(FXE - e) for a per-image max |mask * dcols| below 2^e, FXE = 48); FXB 32: int32
+// fixed point, FXE = 18.  The bound this relies on: every (pixel, tap) sample of the 16 x 16 tile adds at most
+// one corner to a cell, so a cell sums at most 256 K contributions of magnitude below 2^FXE each, and
+// FXE <= 30 - ceil(log2(256 K)) (62 - ... for int64) keeps the sum below 2^30 (2^62): gx_fx_bits() lowers
+// FXE past 16 (64) taps -- at 49 taps 256 x 49 x 2^18 = 3.3e9 would wrap the int32 cell when the samples
+// converge with one sign.  The quantum is 2^-FXE of the image's max |mask * dcols| (the
 // dcols themselves carry bf16 rounding, 2^-9 of each value).  The float -> int64 conversion is ~12 VALU
 // instructions per corner and channel, the int32 one two -- the kernel is VALU-bound on them -- and
 // the int32 image is half the LDS (a wider halo fits).  fp32 LDS atomics are ~25x slower on gfx950.
@@ -1192,7 +1196,7 @@ __global__ void __launch_bounds__(DC8_NT, 2) dcn_coord_dy8_kernel(DcnArgs a, con
 // OCC: 8-wave blocks per CU the registers are budgeted for (launch bounds count waves per SIMD; at 3
 // the int32 kernel spills 22 VGPRs and ran 1.10 vs 1.01 ms for the C5 op fwd + bwd)
 template <int FXB, bool NCHW, int OCC = 2>
-__global__ void __launch_bounds__(DW_NT, 2 * OCC) dcn_gradx_dy8_kernel(DcnArgs a, int R, int RH, int RW,
+__global__ void __launch_bounds__(DW_NT, 2 * OCC) dcn_gradx_dy8_kernel(DcnArgs a, int R, int RH, int RW, int FXE,
                                                                  const bf16_t* __restrict__ dy, int ldy,
                                                                  const bf16_t* __restrict__ wd, int ldw, int cop,
                                                                  const float* __restrict__ off,
@@ -1211,7 +1215,7 @@ __global__ void __launch_bounds__(DW_NT, 2 * OCC) dcn_gradx_dy8_kernel(DcnArgs a
   const bool direct = !(mx <= 3.0e38f);
   int ex = 0;
   frexpf(direct ? 1.f : mx, &ex);
-  const int e = min(127, (FXB == 64 ? 48 : 18) - ex);
+  const int e = min(127, FXE - ex);
   const float sc = ldexpf(1.f, e), isc = ldexpf(1.f, -e);
   const int ho0 = (t / tw) * DX_TT, wo0 = (t - (t / tw) * tw) * DX_TT;
   const int ry0 = ho0 * a.sh - a.ph - R, rx0 = wo0 * a.sw - a.pw - R;
@@ -1332,19 +1336,28 @@ __global__ void __launch_bounds__(DW_NT, 2 * OCC) dcn_gradx_dy8_kernel(DcnArgs a
 }
 
 // Shapes and geometry of the fused backward: coord_win's shapes with Cout <= 64; the coordinate
-// kernel's LDS (offset tile + weight slice + window, R <= 2) and the scatter image (R <= 2) each
-// within 80 KB, two blocks per CU.  (The op layer's SR_DCN_BWD_FUSED=0 keeps the dcols path.)
+// kernel's LDS (weight slices + window, R <= 2) and the scatter image (R <= 4 for the int32 image, <= 2 for
+// the int64 one) each within 80 KB, two blocks per CU.  (The op layer's SR_DCN_BWD_FUSED=0 keeps the dcols path.)
 struct BwdGeom {
   int R1, WH, WW, R2, RH, RW;
   size_t lds1, lds2;
-  int fx;  // fixed-point bits of the scatter image (64 / 32)
+  int fx;   // fixed-point bits of the scatter image (64 / 32)
+  int fxe;  // bits of one contribution in it (gx_fx_bits)
 };
 // Scatter image (A/B): knob SR_DCN_GX_FX=64 the int64 fixed-point image, else int32
 int gx_fx_env() { return sr_knob(K_DCN_GX_FX) == 64 ? 64 : 32; }
+// Bits of one contribution: 18 (48), lowered so that the 256 K contributions a cell can receive stay below
+// 2^30 (2^62): 30 - ceil(log2(256 K)) is 18 up to 16 taps, 17 at 25, 16 at 49.
+int gx_fx_bits(int fx, int K) {
+  int lg = 0;  // ceil(log2(256 K))
+  while ((1ll << lg) < 256ll * K) ++lg;
+  return fx == 64 ? std::min(48, 62 - lg) : std::min(18, 30 - lg);
+}
 
 bool bwd_fused_geom(const sr_dcn_desc* d, const DcnArgs& a, int cop, BwdGeom* bg) {
   if (!coord_win_ok(d, a) || cop < 8 || cop > 64 || cop % 8) return false;
   bg->fx = gx_fx_env();
+  bg->fxe = gx_fx_bits(bg->fx, a.K);
   bool ok1 = false, ok2 = false;
   for (int r = 2; r >= 0 && !ok1; --r) {
     const int wh = (DW_TH - 1) * a.sh + (a.kh - 1) * a.dh + 2 + 2 * r;
@@ -1461,7 +1474,7 @@ int sr_dcn_bwd_fused(const sr_dcn_desc* d, const void* dy, int ldy, const void* 
   const dim3 xg((unsigned)(a.N * xt));
 #define SR_GX(FXB, NC, OC)                                                                                    \
   hipLaunchKernelGGL((dcn_gradx_dy8_kernel<FXB, NC, OC>), xg, dim3(DW_NT), bg.lds2, s, a, bg.R2, bg.RH, bg.RW, \
-                     (const bf16_t*)dy, ldy, (const bf16_t*)wd, ldw, cout_p, offset, mask, (const unsigned*)amax, \
+                     bg.fxe, (const bf16_t*)dy, ldy, (const bf16_t*)wd, ldw, cout_p, offset, mask, (const unsigned*)amax, \
                      grad_x)
   if (bg.fx == 64) { if (nchw) SR_GX(64, true, 2); else SR_GX(64, false, 2); }
   else { if (nchw) SR_GX(32, true, 2); else SR_GX(32, false, 2); }

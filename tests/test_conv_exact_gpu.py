@@ -12,8 +12,8 @@ NaN and the channels around an output slice with a sentinel that must stay bit-u
 holds the case tables (tests/test_exact_grid_host.py proves on the CPU that single defects are rejected).
 
 Not covered, because no operand grid makes them exact in fp32: the GELU ``aux`` store and ``gate_mode=1``,
-LN-fused linears, sigmoid, and DCN's bilinear sampling.  Their conv parts run the same kernels as the plain
-epilogue cases here.
+LN-fused linears and sigmoid.  Their conv parts run the same kernels as the plain epilogue cases here.  DCN's
+bilinear sampling is exact on a quarter-pixel offset lattice and is covered by tests/test_dcn_exact_gpu.py.
 
 One assumption is not provable on the host: that the MFMA units keep multiples of the quantum exact while all
 magnitudes stay below 2^20 quanta.  A mismatch confined to dense large-K cases would point there."""

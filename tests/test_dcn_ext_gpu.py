@@ -5,7 +5,10 @@ arguments (kW before kH, stride / padding / dilation as (w, h) pairs for v1, sca
 ``im2col_step`` = min(step, N), ``scale`` 1), against the float64 numpy oracle (oracle/ops.py).
 
 Also: the op config of BASELINE C5 (x [N, 64, 128, 128], deformable_groups 8; N reduced to 1), the
-v1 im2col_step chunking, and the accumulate semantics of the parameter gradient (+= scale * dW)."""
+v1 im2col_step chunking, and the accumulate semantics of the parameter gradient (+= scale * dW).
+
+The ``exact`` tests repeat this on the operand lattice of tests/_dcn_exact.py, where every result is exactly
+representable: out and all gradients bit for bit, and the accumulation into integer-grid initial buffers."""
 import numpy as np
 import pytest
 import torch
@@ -13,6 +16,8 @@ from torch.autograd import Function
 
 from basicsr4rs_amd.ops import deform_conv_ext
 from oracle import ops as O
+from tests import _dcn_exact as X
+from tests import _exact as E
 from tests.test_ops_gpu import DCN_CASES, _dcn_inputs, rel
 
 pytestmark = pytest.mark.gpu
@@ -206,3 +211,47 @@ def test_offset_conv_general_geometry_on_hip(cuda):
     ref = O.dcn_forward(x.numpy(), off.numpy(), None, m.weight.detach().numpy(), None, 2, 1, 1, 1, 1)
     out = m.to(cuda)(x.to(cuda))
     assert rel(out, ref) < 1e-4, rel(out, ref)
+
+
+@pytest.mark.parametrize('family', ['lattice', 'edges'])
+@pytest.mark.parametrize('cid', X.G_IDS)
+def test_deform_conv_ext_exact(cuda, cid, family):
+    """The drop-in's Functions on quarter-pixel offsets, {0, 1/2, 1} masks and integer maps: out and every gradient
+    equal the float64 oracle bit for bit (tests/test_dcn_exact_host.py shows each case exact on the host)."""
+    b = X.build(cid, family)
+    b.check()
+    N, C, H, W, Cout, k, s, p, d, groups, dg, modulated = b.case
+    t = [None if a is None else a.to(cuda, torch.float32).requires_grad_()
+         for a in (b.x, b.offset, b.mask, b.weight, b.bias)]
+    if modulated:
+        out = _V2.apply(t[0], t[1], t[2], t[3], t[4], s, p, d, groups, dg)
+    else:
+        out = _V1.apply(t[0], t[1], t[3], s, p, d, groups, dg, 64)
+    E.assert_bits(out.detach(), b.y, f'{cid}/{family} out', axes='nchw')
+    out.backward(b.dy.to(cuda, torch.float32))
+    for name, ref, tt in zip(('x', 'offset', 'mask', 'weight', 'bias'), (b.gx, b.goff, b.gmask, b.gw, b.gb), t):
+        if tt is not None:
+            E.assert_bits(tt.grad, ref, f'{cid}/{family} grad {name}', axes='nchw' if ref.dim() == 4 else 'c')
+
+
+@pytest.mark.parametrize('family', ['lattice', 'edges'])
+def test_deform_conv_ext_exact_step_and_accumulate(cuda, family):
+    """v1 with im2col_step 2 over N 4 on the lattice: out bit for bit; gradWeight = grid + 0.5 dW and gradInput =
+    grid + dX exactly, from integer-grid initial buffers (every sum stays a multiple of 1/64 far below 2^24)."""
+    b = X.build('E4', family)
+    b.check()
+    X_, OFF, Wt, DY = (a.to(cuda, torch.float32).contiguous() for a in (b.x, b.offset, b.weight, b.dy))
+    e = X_.new_empty(0)
+    o = torch.full((4, 24, 9, 9), float('nan'), device=cuda)
+    deform_conv_ext.deform_conv_forward(X_, Wt, OFF, o, e, e, 3, 3, 1, 1, 1, 1, 1, 1, 1, 2, 2)
+    E.assert_bits(o, b.y, f'E4/{family} out, im2col_step 2', axes='nchw')
+    gen = E.gen_for(f'dcn_ext/accumulate/{family}')
+    gw0, gx0 = E.grid(b.weight.shape, gen=gen), E.grid(b.x.shape, gen=gen)
+    gw = gw0.to(cuda, torch.float32)
+    deform_conv_ext.deform_conv_backward_parameters(X_, OFF, DY, gw, e, e, 3, 3, 1, 1, 1, 1, 1, 1, 1, 2, 0.5, 2)
+    E.assert_bits(gw, gw0 + 0.5 * b.gw, f'E4/{family} gradWeight = grid + 0.5 dW', axes='oikl')
+    gx = gx0.to(cuda, torch.float32)
+    goff = torch.zeros_like(OFF)
+    deform_conv_ext.deform_conv_backward_input(X_, OFF, DY, gx, goff, Wt, e, 3, 3, 1, 1, 1, 1, 1, 1, 1, 2, 2)
+    E.assert_bits(gx, gx0 + b.gx, f'E4/{family} gradInput = grid + dX', axes='nchw')
+    E.assert_bits(goff, b.goff, f'E4/{family} gradOffset', axes='nchw')
