@@ -699,7 +699,8 @@ int sr_pos_embed_grad(int dtype, const void* dy, int N, int P, int C, int Cp, fl
  * basicsr/ops native extensions (replacements of deform_conv_ext, fused_act_ext,
  * upfirdn2d_ext).
  * ------------------------------------------------------------------------------------- */
-/* Deformable convolution geometry (csrc/dcn.hip).  x is NHWC [N][H][W][Cp] (dtype);
+/* Deformable convolution geometry (csrc/dcn.hip: entry points and geometry; kernels in csrc/dcn_cols.hip,
+ * dcn_fwd_fused.hip and dcn_bwd_win.hip).  x is NHWC [N][H][W][Cp] (dtype);
  * offset [N][DG*2*kh*kw][Ho][Wo] and mask [N][DG*kh*kw][Ho][Wo] are the reference's NCHW
  * fp32 tensors (channel 2*tap = dy, 2*tap+1 = dx, per deformable group).  Columns are
  * pixel-major rows [N*Ho*Wo][groups][kh*kw][cgp] (cgp = padded C/groups), the operand of

@@ -1,4 +1,5 @@
-"""Exact-lattice tests of the deformable conv kernels (csrc/dcn.hip): bit for bit against the float64 oracle.
+"""Exact-lattice tests of the deformable conv kernels (csrc/dcn_cols.hip, dcn_fwd_fused.hip, dcn_bwd_win.hip; entry
+points and geometry in csrc/dcn.hip): bit for bit against the float64 oracle.
 
 Offsets on a quarter-pixel lattice, masks in {0, 1/2, 1} and small-integer maps make every coordinate, bilinear
 weight, column value, gradient term and fixed-point scatter contribution exactly representable (tests/_dcn_exact.py

@@ -1,20 +1,23 @@
 #!/usr/bin/env python3
-"""Are the conv3x3 kernels of two builds the same device code?
+"""Are the kernels of one source family the same device code in two builds?
 
-  tools/kernel_identity.py OBJDIR_A OBJDIR_B      (basicsr4rs_amd/lib/obj of two builds)
+  tools/kernel_identity.py [--prefix NAME] OBJDIR_A OBJDIR_B      (basicsr4rs_amd/lib/obj of two builds)
 
-Unbundles the gfx950 code object of every conv3x3*.o on each side and compares the two sides kernel by kernel, keyed
-by mangled name, whichever object a kernel is in: its register / LDS / scratch / kernarg metadata and its whole
-instruction stream (addresses and the padding after a kernel dropped).  Prints one summary; exit status 1 on any
+Unbundles the gfx950 code object of every NAME*.o (default conv3x3) on each side and compares the two sides kernel
+by kernel, whichever object a kernel is in: its register / LDS / scratch / kernarg metadata and its whole
+instruction stream (addresses and the padding after a kernel dropped).  A kernel is keyed by its demangled name
+without the qualifiers that say only where a name is declared (the anonymous namespace, a family namespace), so that
+moving a kernel or an argument struct between namespaces keeps the key.  Prints one summary; exit status 1 on any
 difference.  The check for a refactor that only moves kernels between sources.
 """
-import glob, os, re, subprocess, sys, tempfile
+import argparse, glob, os, re, subprocess, sys, tempfile
 
 LLVM = os.environ.get("LLVM_BIN", "/opt/rocm/llvm/bin")
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 META = (".vgpr_count", ".agpr_count", ".sgpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size",
         ".kernarg_segment_size", ".max_flat_workgroup_size")
 PAD = re.compile(r"^(\.\.\.|s_nop 0|s_code_end)$")
+QUAL = re.compile(r"\(anonymous namespace\)::|\bsr_dcn::")
 
 
 def run(*cmd):
@@ -22,7 +25,7 @@ def run(*cmd):
 
 
 def kernels_of(obj, tmp):
-    """{mangled name: (metadata dict, [instruction lines])} of one host object with an embedded fat binary"""
+    """{key: (metadata dict, [instruction lines])} of one host object with an embedded fat binary"""
     fb, co = os.path.join(tmp, "fb"), os.path.join(tmp, "co")
     if ".hip_fatbin" not in run(f"{LLVM}/llvm-readelf", "-S", obj):
         return {}  # a host-only source
@@ -45,19 +48,24 @@ def kernels_of(obj, tmp):
             cur = streams.setdefault(m.group(1), [])
         elif cur is not None and line.strip():
             cur.append(line.split("//")[0].strip())
+    names = list(meta)
+    plain = run("c++filt", *names).splitlines() if names else []
     out = {}
-    for name, md in meta.items():
+    for name, dem in zip(names, plain):
         ins = streams[name]
         while ins and PAD.match(ins[-1]):
             ins.pop()
-        out[name] = ({k: md.get(k) for k in META}, ins)
+        key = QUAL.sub("", dem)
+        if key in out:
+            sys.exit(f"{obj}: two kernels with the key {key}")
+        out[key] = ({k: meta[name].get(k) for k in META}, ins)
     return out
 
 
-def side(objdir):
-    objs = sorted(glob.glob(os.path.join(objdir, "conv3x3*.o")))
+def side(objdir, prefix):
+    objs = sorted(glob.glob(os.path.join(objdir, f"{prefix}*.o")))
     if not objs:
-        sys.exit(f"no conv3x3*.o in {objdir}")
+        sys.exit(f"no {prefix}*.o in {objdir}")
     all_k = {}
     with tempfile.TemporaryDirectory() as tmp:
         for o in objs:
@@ -71,12 +79,15 @@ def side(objdir):
 
 
 def main():
-    if len(sys.argv) != 3:
-        sys.exit(__doc__)
-    print(f"A: {sys.argv[1]}")
-    a = side(sys.argv[1])
-    print(f"B: {sys.argv[2]}")
-    b = side(sys.argv[2])
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--prefix", default="conv3x3", help="compare the kernels of PREFIX*.o (default conv3x3)")
+    ap.add_argument("objdir_a")
+    ap.add_argument("objdir_b")
+    args = ap.parse_args()
+    print(f"A: {args.objdir_a}")
+    a = side(args.objdir_a, args.prefix)
+    print(f"B: {args.objdir_b}")
+    b = side(args.objdir_b, args.prefix)
     only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
     both = sorted(set(a) & set(b))
     dmeta = [k for k in both if a[k][0] != b[k][0]]
