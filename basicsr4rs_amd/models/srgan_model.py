@@ -8,8 +8,9 @@ parameters frozen during the generator half, no discriminator weight gradient is
 host synchronisation in the step; the loss log is reduced when read.
 
 Out of scope: ``train.cuda_graph`` (the generator half is conditional on the iteration; one warning, the step
-runs eagerly), distributed training (``dist: true`` is refused: the discriminator's gradient and BatchNorm
-buffer exchange is not built) and ``ldl_opt``.
+runs eagerly) and distributed training (``dist: true`` is refused: the discriminator's gradient and BatchNorm
+buffer exchange is not built).  ``ldl_opt`` is refused here and in ESRGANModel (the reference builds the loss there
+and never uses it); RealESRGANModel overrides ``_build_ldl`` (models/realesrgan_model.py).
 """
 from collections import OrderedDict
 
@@ -53,9 +54,7 @@ class SRGANModel(SRModel):
         self.net_d.train()
 
         self.cri_pix = self.build_optional_loss(train_opt, 'pixel_opt')
-        if train_opt.get('ldl_opt'):
-            raise NotImplementedError(f'{type(self).__name__}: train.ldl_opt is not supported')
-        self.cri_ldl = None
+        self.cri_ldl = self._build_ldl(train_opt)
         self.cri_perceptual = self.build_optional_loss(train_opt, 'perceptual_opt')
         self.cri_gan = self.build_optional_loss(train_opt, 'gan_opt')
         if self.cri_gan is None:
@@ -64,6 +63,12 @@ class SRGANModel(SRModel):
         self.net_d_init_iters = train_opt.get('net_d_init_iters', 0)
         self.setup_optimizers()
         self.setup_schedulers()
+
+    def _build_ldl(self, train_opt):
+        """``train.ldl_opt`` -> ``cri_ldl``; only RealESRGANModel's step has the term."""
+        if train_opt.get('ldl_opt'):
+            raise NotImplementedError(f'{type(self).__name__}: train.ldl_opt is not supported')
+        return None
 
     def setup_optimizers(self):
         train_opt = self.opt['train']
@@ -94,13 +99,17 @@ class SRGANModel(SRModel):
         return current_iter % self.net_d_iters == 0 and current_iter > self.net_d_init_iters
 
     def _g_content_terms(self, loss_dict, pix_gt=None, percep_gt=None):
-        """Pixel and perceptual / style terms of the generator loss and their log entries.  ``pix_gt`` /
+        """Pixel, LDL and perceptual / style terms of the generator loss and their log entries.  ``pix_gt`` /
         ``percep_gt``: the targets in place of ``self.gt`` (models/realesrgan_model.py)."""
         l_g_total = 0
         if self.cri_pix:
             l_g_pix = self.cri_pix(self.output, self.gt if pix_gt is None else pix_gt)
             l_g_total = l_g_total + l_g_pix
             loss_dict['l_g_pix'] = l_g_pix
+        if self.cri_ldl:
+            l_g_ldl = self._ldl_term()
+            l_g_total = l_g_total + l_g_ldl
+            loss_dict['l_g_ldl'] = l_g_ldl
         l_g_total = self._perceptual_terms(l_g_total, loss_dict, keys=('l_g_percep', 'l_g_style'), gt=percep_gt)
         return l_g_total
 

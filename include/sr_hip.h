@@ -386,6 +386,33 @@ int sr_pixel_loss(int kind, int reduction, int pred_dtype, int target_dtype, con
                   const float* weight, int weight_channels, int N, int C, int H, int W, float loss_weight, float eps,
                   float* loss, void* out, void* grad, void* workspace, size_t ws_bytes, void* stream);
 size_t sr_pixel_loss_workspace(int64_t n);
+/* LDL artifact map and the ldl_opt term (csrc/ldl.hip; basicsr/losses/loss_util.py:99-145,
+ * basicsr/models/realesrgan_model.py:211-226).  out / gt / ema: NCHW-contiguous [N,C,H,W]; out of
+ * out_dtype (SR_F32 / SR_BF16), gt and ema SR_F32 or out's dtype.  Per image n and pixel p: r = sum_c |gt - out|,
+ * e = sum_c |gt - ema|, mu and L the mean and the unbiased variance of the 7x7 window of the reflect-padded r,
+ * V_n the unbiased variance of r over the image, P_n = V_n^(1/5), m = (r >= e):  w = P_n L m.
+ *
+ * sr_ldl_map_fwd writes what the backward keeps -- planes: fp32 [4,N,H,W] = r, mu, m L, m; stats: fp32 [N,8] =
+ * mean of r, V, P, S = sum_p m L r, Q = (1/5) V^(-4/5) 2 / (H W - 1) (0 when V == 0: the dP/dV term of a constant
+ * residual map is defined as 0), T, 0, 0 -- and
+ *   l1 == 0: w, fp32 [N,1,H,W] (required);
+ *   l1 != 0: *loss = k sum_n P_n S_n, the L1Loss of (w out, w gt) with k = loss_weight / (N C H W) for
+ *            SR_REDUCE_MEAN and loss_weight for SR_REDUCE_SUM; T = k S; w is written too when not NULL.
+ * sr_ldl_map_bwd writes d out (out's dtype, rounded once from fp32, every element once) through the whole map,
+ * the window variances and V_n included (the reference does not detach w):
+ *   dW != NULL: the gradient of sum_p dW w (dW fp32 [N,1,H,W]); needs the workspace;
+ *   dW == NULL: the gradient of the fused L1 term (reduction / loss_weight as in the forward call).
+ * upstream (may be NULL = 1): an fp32 device scalar every element is multiplied by before the rounding.
+ * ksize must be 7, H and W >= 4, N <= 65535, N C H W < 2^31; pointers element-aligned; workspace:
+ * sr_ldl_map_workspace bytes, 4-byte aligned.  Anything else is SR_EINVAL before any launch.  Fixed summation
+ * orders, no atomics: two runs give the same bits; nothing allocates or synchronises. */
+size_t sr_ldl_map_workspace(int N, int H, int W);
+int sr_ldl_map_fwd(int out_dtype, int gt_dtype, int ema_dtype, const void* out, const void* gt, const void* ema, int N,
+                   int C, int H, int W, int ksize, int l1, int reduction, float loss_weight, float* w, float* planes,
+                   float* stats, float* loss, void* workspace, size_t ws_bytes, void* stream);
+int sr_ldl_map_bwd(int out_dtype, int gt_dtype, const void* out, const void* gt, const float* planes, const float* stats,
+                   const float* dW, const float* upstream, int N, int C, int H, int W, int ksize, int reduction,
+                   float loss_weight, void* dout, void* workspace, size_t ws_bytes, void* stream);
 /* ---------------------------------------------------------------------------------
  * Perceptual / style loss kernels (csrc/perceptual.hip; PerceptualLoss of basicsr/losses/basic_loss.py:147-253
  * over the VGGFeatureExtractor of basicsr/archs/vgg_arch.py).  Feature maps are dense NHWC of dtype
