@@ -249,6 +249,20 @@ SIGNATURES = {
     'sr_poisson_rate': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'sr_poisson_apply': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'sr_jpeg': (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    'sr_bilinear_up2_fwd_scaled': (_i, [_i, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    'sr_bilinear_up2_bwd_scaled': (_i, [_i, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    'sr_conv3s2_prep': (_i, [_i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'sr_conv3s2_fwd': (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    'sr_conv3s2_dgrad': (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'sr_conv3s2_wgrad_workspace': (_sz, [_i, _i, _i, _i, _i]),
+    'sr_conv3s2_wgrad_splits': (_i, [_i, _i, _i, _i, _i]),
+    'sr_conv3s2_wgrad': (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _sz, _vp]),
+    'sr_pool3s2_fwd': (_i, [_i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'sr_pool3s2_bwd': (_i, [_i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'sr_tsa_corr_fwd': (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'sr_tsa_corr_bwd': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'sr_tsa_modulate_fwd': (_i, [_i, _vp, _vp, _vp, _i64, _vp, _vp]),
+    'sr_tsa_modulate_bwd': (_i, [_i, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
 }
 
 _LIB = None

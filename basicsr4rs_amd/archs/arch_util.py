@@ -15,7 +15,8 @@ from torch.nn import init as init
 from torch.nn.modules.batchnorm import _BatchNorm
 
 from ..ops import conv as C
-from ..ops.dcn import ModulatedDeformConvPack, modulated_deform_conv, offset_conv, split_offset_mask
+from ..ops.dcn import (ModulatedDeformConvPack, modulated_deform_conv, modulated_deform_conv_nhwc, offset_conv,
+                       split_offset_mask)
 from ..ops.layout import pixel_unshuffle  # noqa: F401  (re-export, arch_util.py:217-234)
 from ..utils.logger import get_root_logger
 
@@ -111,12 +112,29 @@ class DCNv2Pack(ModulatedDeformConvPack):
     absolute offset above 50 is logged as a warning (the reference's divergence check, a host
     read per call as there).  The reference prefers torchvision.ops.deform_conv2d, whose
     sampling (bilinear, zero outside -1 < h < H, offsets interleaved (h, w) per tap) is the
-    same arithmetic as modulated_deform_conv: here both are the HIP DCNv2 path."""
+    same arithmetic as modulated_deform_conv: here both are the HIP DCNv2 path.
 
-    def forward(self, x, feat):
-        offset, mask = split_offset_mask(offset_conv(self.conv_offset, feat))
+    ``forward`` takes NCHW ``x`` and ``feat`` as the reference; ``forward_nhwc`` takes both as NHWC feature maps
+    (EDVR's arch) and returns NHWC: the DCN kernels read NHWC anyway, so nothing is converted on the way in."""
+
+    def _check_offset(self, offset):
         offset_absmean = torch.mean(torch.abs(offset))
         if offset_absmean > 50:
             get_root_logger().warning(f'Offset abs mean is {offset_absmean}, larger than 50.')
+
+    def forward(self, x, feat):
+        offset, mask = split_offset_mask(offset_conv(self.conv_offset, feat))
+        self._check_offset(offset)
         return modulated_deform_conv(x, offset, mask, self.weight, self.bias, self.stride, self.padding, self.dilation,
                                      self.groups, self.deformable_groups)
+
+    def forward_nhwc(self, x, feat):
+        conv = self.conv_offset
+        if (conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.padding != (1, 1) or conv.dilation != (1, 1)
+                or self.groups != 1):
+            raise NotImplementedError('DCNv2Pack.forward_nhwc: a 3 x 3, stride 1, padding 1 deformable conv without '
+                                      'conv groups is supported')
+        offset, mask = split_offset_mask(C.to_nchw(C.conv3x3(feat, conv), conv.out_channels))
+        self._check_offset(offset)
+        return modulated_deform_conv_nhwc(x, offset, mask, self.weight, self.bias, self.stride, self.padding,
+                                          self.dilation, self.groups, self.deformable_groups)

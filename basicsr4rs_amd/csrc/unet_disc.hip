@@ -300,10 +300,11 @@ struct UpArgs {
   int H, W, CV;      // the SMALL map and its 16-byte vectors per pixel
   uint32_t total;    // vectors of the map a thread writes
   FastDiv fd_cv, fd_w, fd_h;  // of the written map: vectors per pixel, width, height
+  float scale;       // the SCALED kernels multiply the fp32 result by it before the store
 };
 
 // one thread per output vector: y[n][oy][ox] from the 2 x 2 input pixels (near .75, far .25 per axis)
-template <typename T>
+template <typename T, bool SCALED>
 __global__ void __launch_bounds__(UP_T) up2_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, UpArgs a) {
   constexpr int V = Elt<T>::PER16;
   const int W2 = 2 * a.W, H2 = 2 * a.H;
@@ -324,13 +325,14 @@ __global__ void __launch_bounds__(UP_T) up2_fwd_kernel(const T* __restrict__ x, 
     for (int k = 0; k < V; ++k) {
       const float rn = fmaf(0.75f, nn[k], 0.25f * nf[k]), rf = fmaf(0.75f, fn[k], 0.25f * ff[k]);
       o[k] = fmaf(0.75f, rn, 0.25f * rf);
+      if constexpr (SCALED) o[k] *= a.scale;
     }
     up_st<T, V>(y + (size_t)i * V, o);
   }
 }
 
 // one thread per dx vector: the 4 x 4 dy pixels 2j - 1 .. 2j + 2 per axis (clamped), weights .25 .75 .75 .25
-template <typename T>
+template <typename T, bool SCALED>
 __global__ void __launch_bounds__(UP_T) up2_bwd_kernel(const T* __restrict__ dy, T* __restrict__ dx, UpArgs a) {
   constexpr int V = Elt<T>::PER16;
   const int W2 = 2 * a.W, H2 = 2 * a.H;
@@ -360,7 +362,10 @@ __global__ void __launch_bounds__(UP_T) up2_bwd_kernel(const T* __restrict__ dy,
       }
     }
 #pragma unroll
-    for (int k = 0; k < V; ++k) o[k] = fmaf(0.75f, inner[k], 0.25f * outer[k]);
+    for (int k = 0; k < V; ++k) {
+      o[k] = fmaf(0.75f, inner[k], 0.25f * outer[k]);
+      if constexpr (SCALED) o[k] *= a.scale;
+    }
     up_st<T, V>(dx + (size_t)i * V, o);
   }
 }
@@ -439,25 +444,53 @@ int sr_spectral_norm_bwd(const sr_sn_problem* problems, int n, int accumulate, v
 
 int sr_bilinear_up2_fwd(int dtype, const void* x, int N, int H, int W, int C, void* y, void* stream) {
   UpArgs u;
+  u.scale = 1.f;
   if (int rc = up_check("bilinear_up2_fwd", dtype, x, y, N, H, W, C, u, false)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(up_grid(u.total, UP_FWD_BLOCKS));
   if (dtype == SR_BF16)
-    hipLaunchKernelGGL(up2_fwd_kernel<bf16_t>, grid, dim3(UP_T), 0, s, (const bf16_t*)x, (bf16_t*)y, u);
+    hipLaunchKernelGGL((up2_fwd_kernel<bf16_t, false>), grid, dim3(UP_T), 0, s, (const bf16_t*)x, (bf16_t*)y, u);
   else
-    hipLaunchKernelGGL(up2_fwd_kernel<float>, grid, dim3(UP_T), 0, s, (const float*)x, (float*)y, u);
+    hipLaunchKernelGGL((up2_fwd_kernel<float, false>), grid, dim3(UP_T), 0, s, (const float*)x, (float*)y, u);
   return sr_check(hipGetLastError(), "bilinear_up2_fwd launch");
 }
 
 int sr_bilinear_up2_bwd(int dtype, const void* dy, int N, int H, int W, int C, void* dx, void* stream) {
   UpArgs u;
+  u.scale = 1.f;
   if (int rc = up_check("bilinear_up2_bwd", dtype, dy, dx, N, H, W, C, u, true)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(up_grid(u.total, UP_BWD_BLOCKS));
   if (dtype == SR_BF16)
-    hipLaunchKernelGGL(up2_bwd_kernel<bf16_t>, grid, dim3(UP_T), 0, s, (const bf16_t*)dy, (bf16_t*)dx, u);
+    hipLaunchKernelGGL((up2_bwd_kernel<bf16_t, false>), grid, dim3(UP_T), 0, s, (const bf16_t*)dy, (bf16_t*)dx, u);
   else
-    hipLaunchKernelGGL(up2_bwd_kernel<float>, grid, dim3(UP_T), 0, s, (const float*)dy, (float*)dx, u);
+    hipLaunchKernelGGL((up2_bwd_kernel<float, false>), grid, dim3(UP_T), 0, s, (const float*)dy, (float*)dx, u);
+  return sr_check(hipGetLastError(), "bilinear_up2_bwd launch");
+}
+
+int sr_bilinear_up2_fwd_scaled(int dtype, const void* x, int N, int H, int W, int C, float scale, void* y, void* stream) {
+  UpArgs u;
+  u.scale = scale;
+  if (int rc = up_check("bilinear_up2_fwd_scaled", dtype, x, y, N, H, W, C, u, false)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(up_grid(u.total, UP_FWD_BLOCKS));
+  if (dtype == SR_BF16)
+    hipLaunchKernelGGL((up2_fwd_kernel<bf16_t, true>), grid, dim3(UP_T), 0, s, (const bf16_t*)x, (bf16_t*)y, u);
+  else
+    hipLaunchKernelGGL((up2_fwd_kernel<float, true>), grid, dim3(UP_T), 0, s, (const float*)x, (float*)y, u);
+  return sr_check(hipGetLastError(), "bilinear_up2_fwd launch");
+}
+
+int sr_bilinear_up2_bwd_scaled(int dtype, const void* dy, int N, int H, int W, int C, float scale, void* dx, void* stream) {
+  UpArgs u;
+  u.scale = scale;
+  if (int rc = up_check("bilinear_up2_bwd_scaled", dtype, dy, dx, N, H, W, C, u, true)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(up_grid(u.total, UP_BWD_BLOCKS));
+  if (dtype == SR_BF16)
+    hipLaunchKernelGGL((up2_bwd_kernel<bf16_t, true>), grid, dim3(UP_T), 0, s, (const bf16_t*)dy, (bf16_t*)dx, u);
+  else
+    hipLaunchKernelGGL((up2_bwd_kernel<float, true>), grid, dim3(UP_T), 0, s, (const float*)dy, (float*)dx, u);
   return sr_check(hipGetLastError(), "bilinear_up2_bwd launch");
 }
 

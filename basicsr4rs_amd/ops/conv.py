@@ -238,8 +238,26 @@ class ConvSpec:
 
 
 class _Prep:
-    """Cached GEMM images of one (weight, layout) pair and the arguments that rebuild them."""
-    __slots__ = ('weight', 'bias', 'dtype', 'shape', 'maps', 'val', 'key', 'used', '__weakref__')
+    """Cached GEMM images of one (weight, layout) pair and the arguments that rebuild them.  The parameters are
+    held weakly: the entry hangs off the weight's own ``__dict__``, and a strong reference back would make every
+    net a reference cycle, freed (with its GPU memory) only when the cycle collector next runs."""
+    __slots__ = ('_weight', '_bias', 'dtype', 'shape', 'maps', 'val', 'key', 'used', '__weakref__')
+
+    @property
+    def weight(self):
+        return self._weight()
+
+    @weight.setter
+    def weight(self, w):
+        self._weight = weakref.ref(w)
+
+    @property
+    def bias(self):
+        return self._bias() if self._bias is not None else None
+
+    @bias.setter
+    def bias(self, b):
+        self._bias = weakref.ref(b) if b is not None else None
 
 
 # (id(weight), static key) -> _Prep, WEAK: an entry lives as long as its weight (which holds it in
@@ -314,7 +332,8 @@ def refresh_prepared():
     that just ended (call right after ``bump_param_epoch`` by an optimizer step), and re-key
     them to the new epoch so the next forward finds them current.  Graph-capturable."""
     ep = _PARAM_EPOCH[0]
-    live = [e for e in _PREP_ALL.values() if e.used == ep - 1]
+    # (an entry kept only by the last refresh table outlives its weight: skipped)
+    live = [e for e in _PREP_ALL.values() if e.used == ep - 1 and e.weight is not None]
     if not live:
         return
     lib = _lib.load()

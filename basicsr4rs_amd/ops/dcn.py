@@ -21,6 +21,10 @@ Execution (per call, all images at once instead of the reference's per-image loo
             scatter kernels and never stored (``SR_DCN_BWD_FUSED=0`` keeps the dcols path).
 Under ``torch.autocast('cuda')`` samples, columns and GEMMs run in bf16 (fp32 accumulate);
 offsets, masks and all their gradients stay fp32.
+
+``modulated_deform_conv_nhwc`` (EDVR's arch) takes ``x`` as the NHWC feature map the kernels read anyway and
+returns NHWC in the map's dtype: no NCHW round trip on the way in; the fused kernels' NCHW fp32 stores of ``y``
+and grad ``x`` go through the layout kernels at that boundary.
 """
 import math
 
@@ -37,7 +41,8 @@ from .swin import LinearSpec
 from .._switches import switch
 
 __all__ = ['DeformConvFunction', 'ModulatedDeformConvFunction', 'deform_conv', 'modulated_deform_conv', 'DeformConv',
-           'DeformConvPack', 'ModulatedDeformConv', 'ModulatedDeformConvPack', 'offset_conv', 'split_offset_mask']
+           'DeformConvPack', 'ModulatedDeformConv', 'ModulatedDeformConvPack', 'offset_conv', 'split_offset_mask',
+           'modulated_deform_conv_nhwc']
 
 
 def _require_gpu(*tensors):
@@ -132,7 +137,9 @@ def fused_ok(g, dtype):
     return dtype == torch.bfloat16 and bool(_lib.load().sr_dcn_fwd_fused_ok(g.desc(dtype), g.cout))
 
 
-def _dcn_forward(x, offset, mask, weight, bias, g, dtype, need_cols=True):
+def _dcn_forward(x, offset, mask, weight, bias, g, dtype, need_cols=True, nhwc=False):
+    """``nhwc``: ``x`` is already the NHWC map [N, H, W, Cp] of ``dtype`` the kernels read, and the result comes back
+    NHWC in ``dtype`` (the fused kernel's NCHW fp32 store converted by the layout kernel)."""
     lib = _lib.load()
     off = offset.float().contiguous()
     msk = None if mask is None else mask.float().contiguous()
@@ -141,15 +148,15 @@ def _dcn_forward(x, offset, mask, weight, bias, g, dtype, need_cols=True):
     if msk is not None and tuple(msk.shape) != (g.N, g.DG * g.K, g.Ho, g.Wo):
         raise RuntimeError(f'mask shape {tuple(msk.shape)} != {(g.N, g.DG * g.K, g.Ho, g.Wo)}')
     if fused_ok(g, dtype):
-        xh = C.nchw_to_nhwc(x.float(), g.Cp, dtype)
+        xh = x if nhwc else C.nchw_to_nhwc(x.float(), g.Cp, dtype)
         wf, _, bg = _prepared(weight, bias, g, _spec(g), dtype)[0]
         y = torch.empty(g.N, g.cout, g.Ho, g.Wo, device=x.device, dtype=torch.float32)
         cols = torch.empty(g.N, g.Ho, g.Wo, g.L, device=x.device, dtype=dtype) if need_cols else None
         _lib.check(lib.sr_dcn_fwd_fused(g.desc(dtype), _lib.ptr(xh), 0, _lib.ptr(off), _lib.ptr(msk), _lib.ptr(wf),
                                         wf.shape[1], wf.shape[0], g.cout, _lib.ptr(bg if bias is not None else None),
                                         _lib.ptr(y), _lib.ptr(cols), _lib.stream()))
-        return y, (xh, off, msk, cols)
-    xh = C.nchw_to_nhwc(x.float(), g.Cp, dtype)
+        return (C.nchw_to_nhwc(y, g.ldy, dtype) if nhwc else y), (xh, off, msk, cols)
+    xh = x if nhwc else C.nchw_to_nhwc(x.float(), g.Cp, dtype)
     cols = torch.empty(g.N, g.Ho, g.Wo, g.L, device=x.device, dtype=dtype)
     _lib.check(lib.sr_dcn_im2col(g.desc(dtype), _lib.ptr(xh), _lib.ptr(off), _lib.ptr(msk), _lib.ptr(cols),
                                  _lib.stream()))
@@ -159,7 +166,7 @@ def _dcn_forward(x, offset, mask, weight, bias, g, dtype, need_cols=True):
     for gi, (wf, _, bg) in enumerate(images):
         C.conv_fwd_raw(cols, wf, None if bias is None else bg, y, g.N, g.Ho, g.Wo, kc, g.cout_gp, g.cout_gp,
                        ksize=1, ldx=g.L, xcoff=gi * kc, ldy=g.ldy, ycoff=gi * g.cout_gp)
-    return C.nhwc_to_nchw(y, g.cout), (xh, off, msk, cols)
+    return (y if nhwc else C.nhwc_to_nchw(y, g.cout)), (xh, off, msk, cols)
 
 
 BWD_FUSED = switch('SR_DCN_BWD_FUSED') != '0'
@@ -172,12 +179,13 @@ def bwd_fused_ok(g, dtype):
             and bool(_lib.load().sr_dcn_bwd_fused_ok(g.desc(dtype), g.cout_gp)))
 
 
-def _dcn_backward(grad_out, saved, weight, bias, g, dtype):
+def _dcn_backward(grad_out, saved, weight, bias, g, dtype, nhwc=False):
+    """``nhwc``: ``grad_out`` is the NHWC map [N, Ho, Wo, ldy] and grad x comes back NHWC [N, H, W, Cp] in ``dtype``."""
     xh, off, msk, cols = saved
     lib = _lib.load()
     spec = _spec(g)
     images = _prepared(weight, bias, g, spec, dtype)
-    dyh = C.nchw_to_nhwc(grad_out.float(), g.ldy, dtype)
+    dyh = grad_out.to(dtype).contiguous() if nhwc else C.nchw_to_nhwc(grad_out.float(), g.ldy, dtype)
     fused = bwd_fused_ok(g, dtype)
     dcols = None if fused else torch.empty(g.N, g.Ho, g.Wo, g.L, device=dyh.device, dtype=dtype)
     ci_map = spec.maps(dyh.device)[3]
@@ -206,12 +214,12 @@ def _dcn_backward(grad_out, saved, weight, bias, g, dtype):
             lib.sr_dcn_bwd_fused(d, _lib.ptr(dyh), g.ldy, _lib.ptr(wd), wd.shape[1], g.cout_gp, _lib.ptr(xh),
                                  _lib.ptr(off), _lib.ptr(msk), _lib.ptr(gx), 1, _lib.ptr(goff), _lib.ptr(gmask),
                                  _lib.ptr(ws), wsb, _lib.stream()))
-        return gx, goff, gmask, grad_weight, grad_bias
+        return (C.nchw_to_nhwc(gx, g.Cp, dtype) if nhwc else gx), goff, gmask, grad_weight, grad_bias
     gx = torch.zeros(g.N, g.H, g.W, g.Cp, device=dyh.device, dtype=torch.float32)
     _lib.check(
         lib.sr_dcn_col2im(d, _lib.ptr(dcols), _lib.ptr(xh), _lib.ptr(off), _lib.ptr(msk), _lib.ptr(gx),
                           _lib.ptr(goff), _lib.ptr(gmask), _lib.ptr(ws), wsb, _lib.stream()))
-    return C.nhwc_to_nchw(gx, g.C), goff, gmask, grad_weight, grad_bias
+    return (gx.to(dtype) if nhwc else C.nhwc_to_nchw(gx, g.C)), goff, gmask, grad_weight, grad_bias
 
 
 def _save(ctx, g, dtype, x, saved, weight, bias):
@@ -296,8 +304,45 @@ def _with_grad_mode(fn):
     return call
 
 
+class _Shape:
+    """The NCHW shape of an NHWC map, for _Geom."""
+
+    def __init__(self, xh, channels):
+        self.shape = (xh.shape[0], channels, xh.shape[1], xh.shape[2])
+
+
+class ModulatedDeformConvNHWCFunction(Function):
+    """DCNv2 on an NHWC feature map, NHWC result: the kernels read ``xh`` as it is.  Offsets, masks and their
+    gradients stay NCHW fp32.  Padded input channels must be zeros (as every conv here leaves them)."""
+
+    @staticmethod
+    def forward(ctx, xh, offset, mask, weight, bias=None, stride=1, padding=0, dilation=1, groups=1,
+                deformable_groups=1):
+        _require_gpu(xh, offset, mask, weight)
+        dtype = xh.dtype
+        g = _Geom(_Shape(xh, weight.shape[1] * groups), weight, stride, padding, dilation, groups, deformable_groups)
+        if xh.dim() != 4 or xh.shape[-1] != g.Cp or dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f'modulated_deform_conv_nhwc: an fp32 / bf16 NHWC map with {g.Cp} channels is expected, '
+                             f'got {tuple(xh.shape)} {dtype}')
+        if groups != 1:
+            raise NotImplementedError('modulated_deform_conv_nhwc: conv groups other than 1 are not supported')
+        out, saved = _dcn_forward(xh.contiguous(), offset, mask, weight, bias, g, dtype,
+                                  _GRAD[0] and any(ctx.needs_input_grad), nhwc=True)
+        _save(ctx, g, dtype, xh, saved, weight, bias)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        _require_gpu(grad_output)
+        saved, weight, bias = _restore(ctx)
+        gx, goff, gmask, gw, gb = _dcn_backward(grad_output, saved, weight, bias, ctx.g, ctx.dtype, nhwc=True)
+        return (gx, goff, gmask, gw, gb, None, None, None, None, None)
+
+
 deform_conv = _with_grad_mode(DeformConvFunction.apply)
 modulated_deform_conv = _with_grad_mode(ModulatedDeformConvFunction.apply)
+modulated_deform_conv_nhwc = _with_grad_mode(ModulatedDeformConvNHWCFunction.apply)
 
 
 def _offset_conv(conv, x):

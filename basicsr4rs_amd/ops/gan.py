@@ -8,7 +8,8 @@ epoch (ops/conv.py) changes; the weight gradient lands in the FlatParams gradien
 ``grad_target`` / ``grad_ready`` and is not launched for a weight that does not require grad.
 ``conv4s2(x, conv, act, slope, weight)`` fuses a LeakyReLU and takes a weight override (per-call images).
 ``spectral_norm_group(convs, training)``: every spectral-normalised weight of a net from one grouped launch sequence.
-``bilinear_up2(x)``: bilinear x2 (align_corners=False) of an NHWC map, forward and backward.
+``bilinear_up2(x, scale)``: bilinear x2 (align_corners=False) of an NHWC map times an optional scale, forward and
+backward.
 ``batch_norm_act(x, bn, act, slope)``: ``nn.BatchNorm2d`` (affine, tracked running statistics) with an optional
 fused LeakyReLU, in the module's training or eval mode; statistics, gamma, beta and their gradients are fp32.
 ``linear(x, lin, act, slope, spatial)``: a head ``nn.Linear`` on its fp32 parameters; ``spatial`` = H * W of the
@@ -343,43 +344,51 @@ def spectral_norm_group(convs, training, eps=1e-12):
 # --------------------------------------------------------------------------------------------- bilinear x2
 
 
-def bilinear_up2_fwd_raw(x):
+def bilinear_up2_fwd_raw(x, scale=1.0):
     N, H, W, Cc = x.shape
     y = torch.empty(N, 2 * H, 2 * W, Cc, device=x.device, dtype=x.dtype)
     lib = _lib.load()
-    args = (_lib.dtype_code(x.dtype), _lib.ptr(x), N, H, W, Cc, _lib.ptr(y), _lib.stream())
+    head = (_lib.dtype_code(x.dtype), _lib.ptr(x), N, H, W, Cc)
+    if scale == 1.0:
+        fn, args = lib.sr_bilinear_up2_fwd, head + (_lib.ptr(y), _lib.stream())
+    else:
+        fn, args = lib.sr_bilinear_up2_fwd_scaled, head + (float(scale), _lib.ptr(y), _lib.stream())
     # 4 taps per output element; x read once (each element 4 times, from cache), y written
-    _launch('up2_fwd_kernel', 7.0 * y.numel(), x.element_size() * (x.numel() + y.numel()), lib.sr_bilinear_up2_fwd, args,
-            (x, y))
+    _launch('up2_fwd_kernel', 7.0 * y.numel(), x.element_size() * (x.numel() + y.numel()), fn, args, (x, y))
     return y
 
 
-def bilinear_up2_bwd_raw(dy):
+def bilinear_up2_bwd_raw(dy, scale=1.0):
     N, H2, W2, Cc = dy.shape
     dx = torch.empty(N, H2 // 2, W2 // 2, Cc, device=dy.device, dtype=dy.dtype)
     lib = _lib.load()
-    args = (_lib.dtype_code(dy.dtype), _lib.ptr(dy), N, H2 // 2, W2 // 2, Cc, _lib.ptr(dx), _lib.stream())
-    _launch('up2_bwd_kernel', 7.0 * dy.numel(), dy.element_size() * (dx.numel() + dy.numel()), lib.sr_bilinear_up2_bwd,
-            args, (dy, dx))
+    head = (_lib.dtype_code(dy.dtype), _lib.ptr(dy), N, H2 // 2, W2 // 2, Cc)
+    if scale == 1.0:
+        fn, args = lib.sr_bilinear_up2_bwd, head + (_lib.ptr(dx), _lib.stream())
+    else:
+        fn, args = lib.sr_bilinear_up2_bwd_scaled, head + (float(scale), _lib.ptr(dx), _lib.stream())
+    _launch('up2_bwd_kernel', 7.0 * dy.numel(), dy.element_size() * (dx.numel() + dy.numel()), fn, args, (dy, dx))
     return dx
 
 
 class _BilinearUp2(torch.autograd.Function):
 
     @staticmethod
-    def forward(ctx, x):
-        return bilinear_up2_fwd_raw(x)
+    def forward(ctx, x, scale=1.0):
+        ctx.scale = scale
+        return bilinear_up2_fwd_raw(x, scale)
 
     @staticmethod
     def backward(ctx, dy):
-        return bilinear_up2_bwd_raw(dy.contiguous())
+        return bilinear_up2_bwd_raw(dy.contiguous(), ctx.scale), None
 
 
-def bilinear_up2(x):
+def bilinear_up2(x, scale=1.0):
     """``F.interpolate(scale_factor=2, mode='bilinear', align_corners=False)`` of an NHWC feature map
-    [N, H, W, C] (C a multiple of 8, fp32 or bf16) -> [N, 2H, 2W, C], with its backward (a gather, no atomics)."""
+    [N, H, W, C] (C a multiple of 8, fp32 or bf16) -> [N, 2H, 2W, C], with its backward (a gather, no atomics).
+    ``scale``: the result times it in the same pass (EDVR's ``upsample(offset) * 2``); 1 is the plain kernel."""
     _check_map(x, 'bilinear_up2')
-    return _BilinearUp2.apply(x.contiguous())
+    return _BilinearUp2.apply(x.contiguous(), float(scale))
 
 
 # ---------------------------------------------------------------------------------------------- batch norm

@@ -11,6 +11,9 @@ their ``.grad`` into one contiguous gradient buffer, so that
   process group is NCCL; gloo on CPU for tests);
 * Adam + EMA is ONE HIP kernel over the flat vectors (sr_adam_ema), with the DDP 1/world
   average folded in as a gradient scale.
+
+``RangedFusedAdam`` steps contiguous ranges of the flat vector with their own step counts (EDVR's
+``tsa_iter`` freeze); ``FusedAdam`` itself is unchanged by it.
 """
 import math
 
@@ -129,6 +132,100 @@ class FusedAdam(torch.optim.Optimizer):
                 self.fp.view(self.m, i).copy_(st['exp_avg'])
                 self.fp.view(self.v, i).copy_(st['exp_avg_sq'])
         self.nstep = int(max(steps)) if steps else 0
+        self._bind_state()
+
+
+class RangedFusedAdam(FusedAdam):
+    """FusedAdam over contiguous parameter ranges that can be frozen and released independently (EDVR's
+    ``tsa_iter``: everything but ``fusion.*`` is frozen for the first iterations).
+
+    ``range_ids``: one id per parameter of ``flat``; each maximal run of equal ids is a range with its own
+    ``{step, lr, grad_scale}`` device vector and step count.  A range whose parameters all have ``requires_grad``
+    is stepped by ``sr_adam_ema_dev`` on its slice of the flat vectors; a frozen range is skipped -- parameters and
+    moments keep their bits and its step count does not advance, which is what ``torch.optim.Adam`` does for
+    parameters whose gradient is ``None`` -- while its EMA copy still follows.  A range with mixed
+    ``requires_grad`` is an error.  ``state_dict()`` keeps ``torch.optim.Adam``'s layout with each parameter's own
+    ``step`` (a range never stepped reports step 0 with zero moments where torch would have no entry yet).
+    Not graph-capturable: which ranges run is decided on the host each step."""
+
+    def __init__(self, flat, range_ids, lr=1e-3, **kwargs):
+        if len(range_ids) != len(flat.params):
+            raise ValueError('RangedFusedAdam: one range id per parameter is expected')
+        self.ranges = []  # [first param, last param + 1]
+        for i, r in enumerate(range_ids):
+            if i and r == range_ids[i - 1]:
+                self.ranges[-1][1] = i + 1
+            else:
+                self.ranges.append([i, i + 1])
+        self.range_steps = [0] * len(self.ranges)
+        super().__init__(flat, lr, **kwargs)
+        self.range_hyper = [torch.zeros(3, dtype=torch.float32, device=flat.flat.device) for _ in self.ranges]
+        self._range_host = [None] * len(self.ranges)
+
+    def _bind_state(self):
+        self._range_step_t = [torch.tensor(float(n)) for n in self.range_steps]
+        for (a, b), t in zip(self.ranges, self._range_step_t):
+            for i in range(a, b):
+                self.state[self.fp.params[i]] = {'step': t, 'exp_avg': self.fp.view(self.m, i),
+                                                 'exp_avg_sq': self.fp.view(self.v, i)}
+
+    def _active(self):
+        out = []
+        for a, b in self.ranges:
+            req = [p.requires_grad for p in self.fp.params[a:b]]
+            if any(req) != all(req):
+                raise NotImplementedError('RangedFusedAdam: a range with both frozen and trainable parameters')
+            out.append(all(req))
+        return out
+
+    def host_step(self):
+        raise NotImplementedError('RangedFusedAdam: the step is not split into host and device parts (no graph capture)')
+
+    def device_step(self, ema=None, ema_decay=0.0):
+        raise NotImplementedError('RangedFusedAdam: the step is not split into host and device parts (no graph capture)')
+
+    @torch.no_grad()
+    def step(self, closure=None, ema=None, ema_decay=0.0):
+        loss = closure() if closure is not None else None
+        g = self.param_groups[0]
+        b1, b2 = g['betas']
+        lib = _lib.load()
+        off = self.fp.offsets
+        for r, ((a, b), on) in enumerate(zip(self.ranges, self._active())):
+            lo, n = off[a], off[b] - off[a]
+            if not on:
+                if ema is not None:  # the EMA of a frozen range still follows (base_model.py:75-82)
+                    ema.flat[lo:lo + n].mul_(ema_decay).add_(self.fp.flat[lo:lo + n], alpha=1 - ema_decay)
+                continue
+            # the kernel increments the device step itself: upload the count before this step
+            hv = (float(self.range_steps[r]), float(g['lr']), float(self.grad_scale))
+            if hv != self._range_host[r]:
+                self.range_hyper[r].copy_(torch.tensor(hv, dtype=torch.float32))
+            self.range_steps[r] += 1
+            self._range_host[r] = (float(self.range_steps[r]), hv[1], hv[2])
+            self._range_step_t[r].fill_(float(self.range_steps[r]))
+            sl = slice(lo, lo + n)
+            _lib.check(
+                lib.sr_adam_ema_dev(_lib.ptr(self.fp.flat[sl]), _lib.ptr(self.fp.grad[sl]), _lib.ptr(self.m[sl]),
+                                    _lib.ptr(self.v[sl]), _lib.ptr(ema.flat[sl] if ema is not None else None), n,
+                                    _lib.ptr(self.range_hyper[r]), float(b1), float(b2), float(g['eps']),
+                                    float(ema_decay), _lib.stream()))
+        self.nstep = max(self.range_steps)
+        bump_param_epoch()
+        refresh_prepared()
+        return loss
+
+    def load_state_dict(self, state_dict):
+        torch.optim.Optimizer.load_state_dict(self, state_dict)
+        with torch.no_grad():
+            for i, p in enumerate(self.fp.params):
+                st = self.state[p]
+                self.fp.view(self.m, i).copy_(st['exp_avg'])
+                self.fp.view(self.v, i).copy_(st['exp_avg_sq'])
+        self.range_steps = [int(max(float(self.state[self.fp.params[i]]['step']) for i in range(a, b)))
+                            for a, b in self.ranges]
+        self.nstep = max(self.range_steps)
+        self._range_host = [None] * len(self.ranges)
         self._bind_state()
 
 

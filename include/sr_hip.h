@@ -887,6 +887,64 @@ int sr_poisson_apply(const float* img, const float* draw_c, const float* draw_g,
  * coefficients, Y [B][H16/8][W16/8][8][8] followed by Cb and Cr [B][H16/16][W16/16][8][8] each. */
 int sr_jpeg(const float* x, int B, int H, int W, const float* quality, int differentiable, int round255, float* y,
             float* coef, void* stream);
+/* Bilinear x2 with an output scale (EDVR's PCD alignment: upsample(offset) * 2 in one pass): the result of
+ * sr_bilinear_up2_fwd / _bwd times scale, multiplied in fp32 before the one rounding on store. */
+int sr_bilinear_up2_fwd_scaled(int dtype, const void* x, int N, int H, int W, int C, float scale, void* y, void* stream);
+int sr_bilinear_up2_bwd_scaled(int dtype, const void* dy, int N, int H, int W, int C, float scale, void* dx,
+                               void* stream);
+/* ---------------------------------------------------------------------------------
+ * EDVR kernels (csrc/edvr.hip; basicsr/archs/edvr_arch.py).  Feature maps are dense NHWC of dtype (SR_F32 /
+ * SR_BF16), 16-byte aligned, channels multiples of 8, fp32 arithmetic.  Fixed summation orders, no atomics: two
+ * calls give identical bits; nothing allocates or synchronises.  SR_EINVAL for null or misaligned pointers,
+ * non-positive sizes and unsupported channel counts, SR_ETOOBIG when a tensor reaches 2^31 bytes; nothing is
+ * launched then.
+ *
+ * nn.Conv2d(cin, cout, 3, 2, 1) on x [N, H, W, Cin] -> y [N, Ho, Wo, Cout], Ho = (H - 1) / 2 + 1 (odd sizes
+ * included), H, W >= 2, Cin and Cout multiples of 8 from 8 to 512.  An implicit GEMM on MFMA bf16 16x16x32 /
+ * f32 16x16x4 with fp32 sums, the sibling of sr_conv4s2_*.
+ * prep: the GEMM images of the fp32 parameter w [cout_real][cin_real][3][3] in dtype: wf [Cout][9 * Cin] for the
+ *   forward, wd (9 * Cin * Cout elements) for the dgrad: one image [Cin][taps * Cout] per (row, column) parity
+ *   class of the input pixel with 1, 2, 2 and 4 taps; padded channels are zeros.
+ * fwd: y = act(conv + bias), bias fp32 [cout_real] or NULL, act SR_ACT_NONE or SR_ACT_LRELU with slope, applied
+ *   to the fp32 sums; padded output channels are zeros.
+ * dgrad: dx [N, H, W, Cin] from dy [N, Ho, Wo, Cout]; every dx element is written once (a gather over the four
+ *   parity classes, 9 tap products per 4 pixels).
+ * wgrad: dw [cout_real][cin_real][3][3] fp32 = (or += with accumulate) scale * the weight gradient; split K over
+ *   sr_conv3s2_wgrad_splits blocks of output pixels, fp32 partials in ws (sr_conv3s2_wgrad_workspace bytes),
+ *   summed in split order.  The bias gradient is sr_channel_reduce of dy. */
+int sr_conv3s2_prep(int dtype, const float* w, int cout_real, int cin_real, int Cout, int Cin, void* wf, void* wd,
+                    void* stream);
+int sr_conv3s2_fwd(int dtype, const void* x, const void* wf, const float* bias, int N, int H, int W, int Cin, int Cout,
+                   int cout_real, int act, float slope, void* y, void* stream);
+int sr_conv3s2_dgrad(int dtype, const void* dy, const void* wd, int N, int H, int W, int Cin, int Cout, void* dx,
+                     void* stream);
+size_t sr_conv3s2_wgrad_workspace(int N, int H, int W, int Cin, int Cout);
+int sr_conv3s2_wgrad_splits(int N, int H, int W, int Cin, int Cout);
+int sr_conv3s2_wgrad(int dtype, const void* dy, const void* x, int N, int H, int W, int Cin, int cin_real, int Cout,
+                     int cout_real, float scale, int accumulate, float* dw, void* ws, size_t ws_bytes, void* stream);
+/* nn.MaxPool2d(3, 2, 1) and nn.AvgPool2d(3, 2, 1) of x [N, H, W, C] in one pass: y [N, Ho, Wo, 2C] with the max in
+ * channels [0, C) and the average in [C, 2C).  Max: padding never wins, the first maximum in row-major window order
+ * wins, a NaN propagates (torch).  Average: the fp32 window sum divided by 9 everywhere (count_include_pad).
+ * bwd: dx [N, H, W, C] from dy [N, Ho, Wo, 2C], all of it written: per input pixel the max gradient of the (at most
+ *   four) windows that chose it, the choice recomputed from x, plus the sum of their average gradients / 9. */
+int sr_pool3s2_fwd(int dtype, const void* x, int N, int H, int W, int C, void* y, void* stream);
+int sr_pool3s2_bwd(int dtype, const void* x, const void* dy, int N, int H, int W, int C, void* dx, void* stream);
+/* Temporal attention of TSAFusion: emb, aligned [B * T, H, W, C], emb_ref [B, H, W, C] (C <= 512):
+ * prob [B, T, H, W] fp32 = sigmoid(sum_c emb * emb_ref), out [B, H, W, T * C], out[..., t * C + c] =
+ * aligned[b * T + t][...][c] * prob.
+ * bwd, from d_out: d_aligned = d_out * prob, dcorr = (sum_c d_out * aligned) * prob * (1 - prob),
+ *   d_emb = dcorr * emb_ref, d_emb_ref = sum over t ascending of dcorr_t * emb_t. */
+int sr_tsa_corr_fwd(int dtype, const void* emb, const void* emb_ref, const void* aligned, int B, int T, int H, int W,
+                    int C, void* out, float* prob, void* stream);
+int sr_tsa_corr_bwd(int dtype, const void* d_out, const void* emb, const void* emb_ref, const void* aligned,
+                    const float* prob, int B, int T, int H, int W, int C, void* d_aligned, void* d_emb, void* d_emb_ref,
+                    void* stream);
+/* y = feat * sigmoid(attn) * 2 + attn_add over n elements (a multiple of 8); bwd: d_feat = dy * 2 sigmoid(attn),
+ * d_attn = dy * 2 feat * sigmoid(attn) (1 - sigmoid(attn)); the gradient of attn_add is dy itself. */
+int sr_tsa_modulate_fwd(int dtype, const void* feat, const void* attn, const void* attn_add, int64_t n, void* y,
+                        void* stream);
+int sr_tsa_modulate_bwd(int dtype, const void* dy, const void* feat, const void* attn, int64_t n, void* d_feat,
+                        void* d_attn, void* stream);
 
 #ifdef __cplusplus
 }
