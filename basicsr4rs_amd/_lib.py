@@ -147,6 +147,9 @@ SIGNATURES = {
     'sr_ldl_map_workspace': (_sz, [_i, _i, _i]),
     'sr_ldl_map_fwd': (_i, [_i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'sr_ldl_map_bwd': (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
+    'sr_registered_loss_workspace': (_sz, [_i, _i, _i, _i, _i]),
+    'sr_registered_loss': (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _sz,
+                                _vp]),
     'sr_maxpool2_fwd': (_i, [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'sr_maxpool2_bwd': (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'sr_gram_kblock': (_i, []),

@@ -413,6 +413,32 @@ int sr_ldl_map_fwd(int out_dtype, int gt_dtype, int ema_dtype, const void* out, 
 int sr_ldl_map_bwd(int out_dtype, int gt_dtype, const void* out, const void* gt, const float* planes, const float* stats,
                    const float* dW, const float* upstream, int N, int C, int H, int W, int ksize, int reduction,
                    float loss_weight, void* dout, void* workspace, size_t ws_bytes, void* stream);
+/* RegisteredLoss (csrc/regloss.hip; basicsr/losses/align_loss.py:161-256): the smallest, per image,
+ * of the L1 / MSE losses between every sub-pixel shift of pred and the target, fused with its gradient.
+ * pred / target: NCHW-contiguous [B,C,H,W]; pred of pred_dtype (SR_F32 / SR_BF16), target SR_F32 or pred's dtype.
+ * taps: fp32 [S,K] on the device, K = 2r + 1 odd, one row of 1-D taps per shift value; the same table serves both
+ * axes and the kernels take it as data.  Shift s = sy * S + sx (the y index is the slow one) is the
+ * cross-correlation with zero padding
+ *   shifted[b,s,c,h,w] = sum_j sum_i taps[sy,j] taps[sx,i] pred[b,c,h+j-r,w+i-r],
+ * scored on the crop [r,H-r) x [r,W-r) only: loss[b,s] = mean over c and the crop of phi(shifted - target),
+ * phi = |d| (SR_LOSS_L1) or d^2 (SR_LOSS_MSE).  idx[b] (int32 [B]) = argmin_s loss[b,s] of the fp32 values, the
+ * first index on ties, a NaN entry before any number (torch.argmin).  table (may be NULL): fp32 [B,S*S] = loss[b,s].
+ *   SR_REDUCE_MEAN  *loss = loss_weight * mean_b loss[b,idx[b]]
+ *   SR_REDUCE_SUM   *loss = loss_weight * sum_b
+ *   SR_REDUCE_NONE  loss[b] = loss_weight * loss[b,idx[b]]   (fp32 [B])
+ * grad (may be NULL), pred's dtype, every element written once: the gradient through the selected shift alone,
+ *   d pred[b,c,p,q] = sum_j sum_i taps[sy*,j] taps[sx*,i] g[b,c,p-j+r,q-i+r],  g = k phi'(d) / n on the crop, 0 on the
+ * border strips (whose pixels of pred do receive gradient), n = C (H-2r)(W-2r), phi' = sign(d) with sign(0) = 0, or
+ * 2d, k = loss_weight / B (mean) or loss_weight (sum; and none, where the caller multiplies image b by its upstream
+ * element).  No shifted image is stored: the workspace (sr_registered_loss_workspace bytes, 8-byte aligned) holds
+ * per-tile partial sums only, nothing the call touches grows with S*S*H*W.  S 1 to 9, K odd 7 to 13, H and W >= K,
+ * B*C*H*W < 2^31, pointers element-aligned; anything else is SR_EINVAL with a message before any launch.  Sums have
+ * a fixed order (double past the tile, no atomics): two runs give the same bits; nothing synchronises or allocates
+ * and idx is read back on the device, so the call can be captured in a HIP graph. */
+size_t sr_registered_loss_workspace(int B, int C, int H, int W, int S);
+int sr_registered_loss(int kind, int reduction, int pred_dtype, int target_dtype, const void* pred, const void* target,
+                       const float* taps, int S, int K, int B, int C, int H, int W, float loss_weight, float* loss,
+                       int* idx, float* table, void* grad, void* workspace, size_t ws_bytes, void* stream);
 /* ---------------------------------------------------------------------------------
  * Perceptual / style loss kernels (csrc/perceptual.hip; PerceptualLoss of basicsr/losses/basic_loss.py:147-253
  * over the VGGFeatureExtractor of basicsr/archs/vgg_arch.py).  Feature maps are dense NHWC of dtype
