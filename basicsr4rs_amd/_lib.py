@@ -94,6 +94,19 @@ class ConvKDesc(ctypes.Structure):
                 ('Cout_real', _i), ('act', _i), ('alpha', _f), ('scale', _f), ('accumulate', _i)]
 
 
+class EcbBlock(ctypes.Structure):
+    _fields_ = ([(n, _vp) for n in ('w3', 'b3', 'k0', 'b0', 'k1', 'b1')] +
+                [(n, _vp * 3) for n in ('ek0', 'eb0', 'escale', 'ebias', 'emask')] +
+                [(n, _vp) for n in ('rk', 'rb', 'wf', 'wd', 'bias_g', 'drk', 'drb', 'g_w3', 'g_b3', 'g_k0', 'g_b0', 'g_k1',
+                                    'g_b1')] + [(n, _vp * 3) for n in ('g_ek0', 'g_eb0', 'g_escale', 'g_ebias')] +
+                [('g_act', _vp)] + [(n, _i) for n in ('Cin', 'Cout', 'mid', 'Cin_p', 'Cout_p', 'with_idt')])
+
+
+class EcbConvDesc(ctypes.Structure):
+    _fields_ = [('dtype', _i), ('mode', _i), ('N', _i), ('H', _i), ('W', _i), ('Cin', _i), ('Cout', _i), ('Cout_real', _i),
+                ('ps', _i), ('img_c', _i)]
+
+
 class DcnDesc(ctypes.Structure):
     _fields_ = [('dtype', _i), ('N', _i), ('C', _i), ('H', _i), ('W', _i), ('Cp', _i), ('Ho', _i), ('Wo', _i),
                 ('kh', _i), ('kw', _i), ('stride_h', _i), ('stride_w', _i), ('pad_h', _i), ('pad_w', _i),
@@ -266,6 +279,13 @@ SIGNATURES = {
     'sr_tsa_corr_bwd': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'sr_tsa_modulate_fwd': (_i, [_i, _vp, _vp, _vp, _i64, _vp, _vp]),
     'sr_tsa_modulate_bwd': (_i, [_i, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    'sr_ecb_table_check': (_i, [ctypes.POINTER(EcbBlock), _i]),
+    'sr_ecb_rep_fwd': (_i, [_i, _vp, _i, _i, _vp]),
+    'sr_ecb_rep_bwd': (_i, [_vp, _i, _i, _i, _vp]),
+    'sr_ecb_conv_blocks': (_i, [ctypes.POINTER(EcbConvDesc)]),
+    'sr_ecb_conv': (_i, [ctypes.POINTER(EcbConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'sr_ecb_da_reduce': (_i, [_vp, _i, _vp, _i, _i, _vp]),
+    'sr_ecb_tail_bwd': (_i, [_i, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
 _LIB = None

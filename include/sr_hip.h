@@ -972,6 +972,92 @@ int sr_tsa_modulate_fwd(int dtype, const void* feat, const void* attn, const voi
 int sr_tsa_modulate_bwd(int dtype, const void* dy, const void* feat, const void* attn, int64_t n, void* d_feat,
                         void* d_attn, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * ECBSR on its collapsed form (csrc/ecb.hip).  An ECB block (basicsr/archs/ecbsr_arch.py) is a 3x3 conv plus
+ * four 1x1 -> 3x3 sequences (a free 3x3 with mid_planes channels; Sobel-x, Sobel-y and Laplacian depthwise
+ * masks times a per-channel scale), every 1x1 output padded with its own bias; the sum is one 3x3 conv with
+ *   RK[o][i][t] = W3 + sum_m k1[o][m][t] k0[m][i] + sum_e scale_e[o] mask_e[o][t] k0_e[o][i] (+ 1 at o == i,
+ *                 centre tap, with_idt)
+ *   RB[o] = b3 + sum_m (sum_t k1[o][m][t]) b0[m] + b1 + sum_e (scale_e[o] (sum_t mask_e[o][t]) b0_e[o] + bias_e[o]).
+ * A net's blocks are described by a table of sr_ecb_block in DEVICE memory (all pointers device pointers, fp32
+ * unless noted), built once; sr_ecb_table_check validates a HOST copy of it (channels 1 .. 64, mid_planes
+ * 1 .. 256, padded counts the next multiples of 8, no null parameter or image pointer) before it is uploaded.
+ * ------------------------------------------------------------------------------- */
+typedef struct sr_ecb_block {
+  const float* w3;        /* conv3x3.weight [Cout][Cin][3][3] */
+  const float* b3;        /* conv3x3.bias [Cout] */
+  const float* k0;        /* conv1x1_3x3: k0 [mid][Cin], b0 [mid], k1 [Cout][mid][3][3], b1 [Cout] */
+  const float* b0;
+  const float* k1;
+  const float* b1;
+  const float* ek0[3];    /* edge branches sbx, sby, lpl: k0 [Cout][Cin], b0 [Cout], scale [Cout], bias [Cout], */
+  const float* eb0[3];    /* mask [Cout][3][3] (read, never assumed) */
+  const float* escale[3];
+  const float* ebias[3];
+  const float* emask[3];
+  float* rk;              /* out: collapsed weight [Cout][Cin][3][3] */
+  float* rb;              /* out: collapsed bias [Cout] */
+  void* wf;               /* out: forward GEMM image [Cout_p][P 9 Cin_p], K = (part 9 + tap) Cin_p + ci, feature dtype */
+  void* wd;               /* out: input-gradient image [Cin_p][P 9 Cout_p], taps flipped, feature dtype */
+  float* bias_g;          /* out: RB padded to [Cout_p] */
+  const float* drk;       /* backward in: dRK [Cout][Cin][3][3], dRB [Cout] */
+  const float* drb;
+  float* g_w3;            /* backward out: the gradients, in the order of the parameters above */
+  float* g_b3;
+  float* g_k0;
+  float* g_b0;
+  float* g_k1;
+  float* g_b1;
+  float* g_ek0[3];
+  float* g_eb0[3];
+  float* g_escale[3];
+  float* g_ebias[3];
+  float* g_act;           /* PReLU slope gradient [Cout] (sr_ecb_da_reduce) or NULL */
+  int Cin, Cout, mid, Cin_p, Cout_p, with_idt;
+} sr_ecb_block;
+int sr_ecb_table_check(const sr_ecb_block* host_table, int L);
+/* One launch over all L blocks (grid max_cout_p x L): rk, rb, and the images wf / wd / bias_g in `dtype`
+ * (padded rows and columns exactly zero).  fp32 arithmetic in a fixed order.  fp32 images have P = 1 part, the
+ * sr_convk_fwd layout; bf16 images P = 2: part 0 is RK rounded to bf16 (hi), part 1 the rounded remainder
+ * RK - hi (lo), which the conv multiplies with the same nine taps -- the collapsed weight is not a bf16 number
+ * even when every parameter is, and hi + lo keeps it to ~2^-17. */
+int sr_ecb_rep_fwd(int dtype, const sr_ecb_block* table, int L, int max_cout_p, void* stream);
+/* The transpose, one launch (grid max_units x L, max_units >= every Cout + mid): from drk / drb the gradients of
+ * the 18 trainable tensors of every block, written (accumulate 0) or added in place (1); every element by one
+ * thread in a fixed order, no atomics.
+ *   dW3 = dRK; db3 = db1 = dbias_e = dRB; dk1[o][m][t] = sum_i dRK[o][i][t] k0[m][i] + dRB[o] b0[m];
+ *   dk0[m][i] = sum_{o,t} dRK[o][i][t] k1[o][m][t]; db0[m] = sum_o dRB[o] sum_t k1[o][m][t];
+ *   dscale_e[o] = sum_i (sum_t dRK[o][i][t] mask_e[o][t]) k0_e[o][i] + dRB[o] (sum_t mask_e) b0_e[o];
+ *   dk0_e[o][i] = scale_e[o] sum_t mask_e[o][t] dRK[o][i][t]; db0_e[o] = scale_e[o] (sum_t mask_e) dRB[o]. */
+int sr_ecb_rep_bwd(const sr_ecb_block* table, int L, int max_units, int accumulate, void* stream);
+/* 3x3 conv, stride 1, zero padding 1, on dense NHWC maps of `dtype` with padded channel counts Cin, Cout
+ * (multiples of 8, <= 64), any N, H, W >= 1; w is a GEMM image [Cout][P 9 Cin] as written by sr_ecb_rep_fwd.
+ *   mode 0  z = conv + bias; y = z > 0 ? z : slope[c] z (slope NULL: y = z).  y, and z unless NULL, are stored
+ *           [N][H][W][Cout]; padded channels exactly zero.  slope has Cout_real entries.
+ *   mode 1  the network tail: out[n][c][h ps + i][w ps + j] = conv[q] + bias[q] + img[n][img_c == 1 ? 0 : c][h][w],
+ *           q = c ps^2 + i ps + j < Cout_real; img, out fp32 NCHW.
+ *   mode 2  the input gradient on the flipped transposed image wd (x = the consumer's dz, Cout = the producer's
+ *           padded channels): y = g * (z > 0 ? 1 : slope[c]) with g the conv and z the producer's stored
+ *           pre-activation (NULL: y = g; at z == 0 the gate is the slope, as torch); with `parts`
+ *           [sr_ecb_conv_blocks(d)][64] each block also writes its channel sums of g * min(z, 0). */
+typedef struct sr_ecb_conv_desc {
+  int dtype;
+  int mode;
+  int N, H, W;
+  int Cin, Cout, Cout_real;
+  int ps;     /* mode 1 */
+  int img_c;  /* mode 1 */
+} sr_ecb_conv_desc;
+int sr_ecb_conv_blocks(const sr_ecb_conv_desc* d);
+int sr_ecb_conv(const sr_ecb_conv_desc* d, const void* x, const void* w, const float* bias, const float* slope, void* y,
+                void* z, float* parts, const float* img, float* out, void* stream);
+/* g_act[c] (+)= sum over the nblocks partial rows of layer l (parts [layers][nblocks][64]) for the first `layers`
+ * table entries whose g_act is not NULL; fixed order. */
+int sr_ecb_da_reduce(const sr_ecb_block* table, int layers, const float* parts, int nblocks, int accumulate, void* stream);
+/* dz[n][h][w][q] = dOut[n][q / s^2][h s + i][w s + j], q = c s^2 + i s + j < C s^2 (pixel-unshuffle of the fp32
+ * NCHW output gradient into the NHWC map of `dtype` with Cp >= C s^2 channels, the rest zero). */
+int sr_ecb_tail_bwd(int dtype, const float* dout, int N, int C, int H, int W, int s, int Cp, void* dz, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
